@@ -1,20 +1,26 @@
 #!/usr/bin/env python3
 """Benchmark of the STFT filter-bank hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the batched compute_full kernel over one batch of synthetic
 utterances already resident in HBM.  Workload at N = 1: BASELINE.json configs[1]
 (1024 x 10 s, 16 kHz float32, 40 triangular mel filters, Hann, 25/10 ms, log power).
 For N > 1 the driver launches one rank per GPU with torch.distributed.run; utterances
 shard across ranks (each rank a full 1024-utterance batch: weak scaling), no data-path
-collective in the timed region.  A second, separately reported region adds the RCCL
-gather of the feature matrices.
+collective in the timed region.
 
 Prints ONE JSON line (rank 0) with the fields the driver expects plus `roofline` (HBM
-bound, algorithmic bytes / kernel time measured with events on the launch stream) and
-`cpu_baseline` (the oracle's vectorised numpy restatement timed on host cores, a bounded
-sample; rank 0, N = 1 only).
+bound, algorithmic bytes / kernel time measured with events on the launch stream).  A
+plain run sets up, pre-rolls and warms up, times exactly K steps and prints the line.
+--dump-outputs DIR writes the features of the last timed step as DIR/<name>.npy (a fixed,
+seeded sample of whole utterances where they exceed 64 MB).  --full adds the legs beyond
+the headline, after the timed region: `roofline.power` (socket power and shader clock over
+1.2 s of extra steps), `cpu_baseline` (the oracle's vectorised numpy restatement timed on
+host cores, a bounded sample; rank 0, N = 1 only), `outputs_finite` and
+`parity_spot_check` (rows of the timed buffer against the oracle), and for N > 1
+`with_gather` (a second, separately timed region that adds the RCCL gather of the
+feature matrices).
 """
 import argparse
 import json
@@ -355,11 +361,50 @@ def _emit(saved_fd, line):
     print(line, flush=True)
 
 
-def main():
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: all files together (npy headers aside)
+DUMP_SEED = 4242  # --dump-outputs: the utterance sample of an output larger than the budget
+
+
+def dump_outputs(dirname, arrays, row_offsets, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """Writes `arrays` (name -> (rows, cols) float32 / float64 tensor whose rows belong to utterance b from
+    row_offsets[b] to row_offsets[b + 1]) as dirname/<name>.npy.  Whole when they fit `budget`, else the
+    rows of a fixed, seeded sample of whole utterances, in batch order, as many as fit.  Returns the
+    indices of the utterances written."""
+    import numpy as np
+    import torch
+
+    row_offsets = np.asarray(row_offsets, dtype=np.int64)
+    counts = np.diff(row_offsets)
+    bytes_per_row = sum(a.shape[1] * a.element_size() for a in arrays.values())
+    if int(row_offsets[-1]) * bytes_per_row <= budget:
+        picks = np.arange(len(counts))
+    else:
+        order = np.random.default_rng(seed).permutation(len(counts))
+        fits = np.cumsum(counts[order]) * bytes_per_row <= budget
+        picks = np.sort(order[fits])
+    rows = np.concatenate([np.arange(row_offsets[b], row_offsets[b + 1]) for b in picks] + [np.zeros(0, np.int64)])
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        host = a.index_select(0, torch.from_numpy(rows).to(a.device)).cpu().numpy()
+        if host.dtype not in (np.float32, np.float64):
+            raise TypeError(f"{name}: {host.dtype} is neither float32 nor float64")
+        np.save(os.path.join(dirname, name + ".npy"), host)
+    return picks
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the features of the last one as DIR/<name>.npy (float32; "
+                         "CMVN workloads also the float64 normalised ones); an output over 64 MB in all is "
+                         "sampled: whole utterances, a fixed seeded choice (rank 0's shard for N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beyond the headline figure, after the timed region: power probe, CPU "
+                         "baseline, finite check and parity spot check of the timed buffer, RCCL gather (N > 1); "
+                         "the --no-* options below leave out single ones of them")
     ap.add_argument("--no-power-probe", action="store_true",
                     help="skip the 1.2 s of extra steps under which socket power and shader clock are sampled")
     ap.add_argument("--preroll-ms", type=float, default=60.0,
@@ -392,7 +437,14 @@ def main():
                     help="force the direct-DFT kernel (si workloads: direct time-domain filtering)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, one GPU per rank) or gloo (rehearsal: every rank on GPU 0, no gather)")
+    return ap
+
+
+def main():
+    ap = build_parser()
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     saved_stdout = _stdout_to_stderr()
     rank = int(os.environ.get("RANK", "0"))
@@ -475,9 +527,11 @@ def main():
         signal = signal.clamp_(-32768, 32767).to(torch.int16)
     if is_si:
         layout = None
-        frames = int(sum(comp.num_frames(int(v)) for v in lengths))
+        row_offsets = np.concatenate([[0], np.cumsum([comp.num_frames(int(v)) for v in lengths])]).astype(np.int64)
+        frames = int(row_offsets[-1])
     else:
         layout = comp.prepare_layout(offsets, lengths, device=dev)
+        row_offsets = layout.row_offsets
         frames = layout.total_rows
     C = comp.num_coeffs
     out_cols = 3 * C if post == "deltas2" else C
@@ -578,9 +632,19 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    finite = bool(torch.isfinite(out).all().item())
+    if args.dump_outputs and rank == 0:
+        # the buffer the steps wrote (the padded one of the deltas launch when PDS_BENCH_OUT_PAD is set)
+        padded = out_wide is not None and deltas is not None and not args.two_launch_deltas and not args.generic
+        feats = out_wide[:, :out_cols] if padded else out
+        arrays = {"features": feats}
+        if cmvn_out is not None:
+            arrays["cmvn"] = cmvn_out
+        picks = dump_outputs(args.dump_outputs, arrays, row_offsets)
+        print("bench.py: wrote %s of %d of %d utterances to %s" % (", ".join(n + ".npy" for n in arrays), len(picks),
+                                                                 B, args.dump_outputs), file=sys.stderr, flush=True)
+    finite = bool(torch.isfinite(out).all().item()) if args.full else None
     power = None
-    if rank == 0 and world == 1 and not args.no_power_probe:
+    if args.full and rank == 0 and world == 1 and not args.no_power_probe:
         try:
             power = power_probe(step, lambda: torch.cuda.synchronize(dev))
         except Exception as exc:  # an optional leg
@@ -590,11 +654,11 @@ def main():
     # 0.308 ms per step against 0.269 ms for the same kernel (rocprofv3 kernel trace, profiles/r2d_*), i.e.
     # the line under-reported the GPU by 13 %.  Workers are spawned, not forked, so HIP being initialised in
     # this process does not matter to them.
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not is_si:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not is_si:
         torch.cuda.synchronize(dev)
         cpu = cpu_baseline(comp, n)
     spot = None
-    if rank == 0 and not is_si:
+    if args.full and rank == 0 and not is_si:
         spot = parity_spot_check(comp, signal, offsets, lengths, layout, out, num_deltas=2 if deltas is not None else 0,
                                  preemph=args.preemph)
 
@@ -619,7 +683,7 @@ def main():
         return gather
 
     gather = None
-    if use_dist and not args.no_gather:
+    if args.full and use_dist and not args.no_gather:
         try:
             gather = timed_gather()
         except Exception as exc:  # the headline number must survive a failing optional leg

@@ -6,7 +6,7 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 wl=${1:-fbank40_16k_25_10_b1024x10s}
 one() {  # label, lib, PF env
-  PDS_STFT_PF=$3 PDS_AMD_LIB=$PWD/$2 timeout -k 5 200 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-gather --workload $wl 2>/dev/null | python -c "
+  PDS_STFT_PF=$3 PDS_AMD_LIB=$PWD/$2 timeout -k 5 200 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-gather --workload $wl 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); c=d.get('parity_spot_check',{}); print('$1', 'frames/s %.4g kernel_ms %.4f min %.4f frac %.3f parity %s %.3g' % (d['value'], d['roofline']['kernel_ms_avg'], d['roofline']['kernel_ms_min'], d['roofline']['frac'], c.get('pass'), c.get('max_err_over_tolerance', -1)))"
 }
 for rep in 1 2 3; do

@@ -11,8 +11,9 @@ for key in ("kernel_ms", "host_enqueue_ms"):
     print("%-9s %-16s" % (sys.argv[1], key), "deciles(ms):", " ".join("%.3f" % x for x in q), " max %.3f" % max(v))
 PY
 }
+steps=$(mktemp -d)
 for i in 1 2; do
-  PDS_BENCH_DUMP_STEPS=gpurun_out/steps_cpu.json python bench.py --steps 300 > /dev/null 2>&1; show with-cpu gpurun_out/steps_cpu.json
-  PDS_BENCH_DUMP_STEPS=gpurun_out/steps_nocpu.json python bench.py --steps 300 --no-cpu-baseline > /dev/null 2>&1; show no-cpu gpurun_out/steps_nocpu.json
+  PDS_BENCH_DUMP_STEPS=$steps/cpu.json python bench.py --full --steps 300 > /dev/null 2>&1; show with-cpu $steps/cpu.json
+  PDS_BENCH_DUMP_STEPS=$steps/nocpu.json python bench.py --full --steps 300 --no-cpu-baseline > /dev/null 2>&1; show no-cpu $steps/nocpu.json
 done
 rocm-smi --showpower --showclocks 2>/dev/null | head -20

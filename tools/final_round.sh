@@ -5,7 +5,7 @@
 TAG=${1:-r3z}
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
-timeout -k 10 300 python bench.py > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err; echo "bench done rc=$?"
+timeout -k 10 300 python bench.py --full > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err; echo "bench done rc=$?"
 bash profiles/run_profile.sh $TAG > $O/${TAG}_profile.log 2>&1; echo "headline profile done rc=$?"
 python profiles/summarize.py $O/prof_$TAG > $O/${TAG}_wave_kernel_summary.txt 2>&1; cp $O/prof_$TAG/stats/stats_kernel_stats.csv $O/${TAG}_kernel_stats.csv
 for w in fbank80_energy_deltas2_b1024x10s:c3 gammatone64_48k_cmvn_b256x10s:c5; do
