@@ -312,6 +312,30 @@ int32_t pds_feed_unpack(pds_feed *feed, int32_t slot, void *dst, int64_t bytes, 
 int32_t pds_feed_release(pds_feed *feed, int32_t slot);
 
 /* ---------------------------------------------------------------------------------
+ * Batched streaming (compute_chunk of many streams per launch; multistream.py::StreamBatch).  The carried samples of
+ * `capacity` streams live in a device pool T[2][capacity][frame_length]: stream s's carry is in half h of its slot,
+ * pool + (h * capacity + s) * frame_length, and a tick reads one half and writes the other (ping-pong).
+ * pds_multistream_assemble builds one tick's packed work buffer and the new carries in one launch.  d_meta holds n
+ * entries of 8 int64:
+ *   [0] stream s   [1] chunk offset in d_chunks   [2] chunk length   [3] carry length c (< frame_length)
+ *   [4] drop d (first samples of the chunk skipped, frame_shift > frame_length)
+ *   [5] new-carry start nc in the work span (avail - nc < frame_length, avail = c + chunk length - d)
+ *   [6] work offset: the span goes to d_work[work offset .. + avail)   [7] half h the carry is read from
+ * and writes work[j] = j < c ? pool[h][s][j] : chunks[chunk offset + d + j - c] for j < avail, and
+ * pool[1 - h][s][j - nc] = work[j] for nc <= j < avail.  The entries' samples are dealt in tiles of
+ * pds_multistream_tile() samples: d_tile_prefix (int64[n + 1]) is the first tile of each entry (exclusive prefix sum of
+ * ceil(avail / tile)), total_tiles its last element.  Streams of one call are distinct.  The features of the tick then
+ * come from pds_stft_batch_* over d_work with explicit frame counts, one call per left reflection (pad_left).
+ * --------------------------------------------------------------------------------- */
+int32_t pds_multistream_tile(void);
+int32_t pds_multistream_assemble_f32(const float *d_chunks, float *d_pool, int64_t capacity, int32_t frame_length,
+                                     const int64_t *d_meta, const int64_t *d_tile_prefix, int32_t n,
+                                     int64_t total_tiles, float *d_work, void *stream);
+int32_t pds_multistream_assemble_f64(const double *d_chunks, double *d_pool, int64_t capacity, int32_t frame_length,
+                                     const int64_t *d_meta, const int64_t *d_tile_prefix, int32_t n,
+                                     int64_t total_tiles, double *d_work, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Pre-processors as separate passes (reference pre.py:67-149); `preemph` above fuses the
  * first one into the frame load instead.
  * pds_preemphasize: per utterance of a packed buffer (offsets/lengths as in pds_stft_batch),

@@ -171,6 +171,12 @@ SIGNATURES = {
     "pds_feed_collect": (c_int32, [c_void_p, c_int32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int64)]),
     "pds_feed_unpack": (c_int32, [c_void_p, c_int32, c_void_p, c_int64, c_int32]),
     "pds_feed_release": (c_int32, [c_void_p, c_int32]),
+    # batched streaming (multistream.py)
+    "pds_multistream_tile": (c_int32, []),
+    "pds_multistream_assemble_f32": (
+        c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
+    "pds_multistream_assemble_f64": (
+        c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
     # multi-GPU gather over RCCL
     "pds_comm_unique_id": (c_int32, [c_void_p]),
     "pds_comm_init_rank": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_void_p)]),

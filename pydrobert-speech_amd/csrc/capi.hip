@@ -38,7 +38,7 @@ using pds::invalid;
 
 extern "C" {
 
-int32_t pds_version(void) { return 100; }
+int32_t pds_version(void) { return 101; }
 
 const char *pds_last_error(void) { return pds::g_last_error.c_str(); }
 

@@ -1,0 +1,378 @@
+"""Batched streaming: ``compute_chunk`` / ``finalize`` of many streams per launch
+
+:func:`ShortTimeFourierTransformFrameComputer.compute_chunk` serves one stream per call: one host concatenation, one
+launch and one synchronisation for what is, for a 10 ms chunk, one frame.  :class:`StreamBatch` keeps the carried
+samples of up to `capacity` streams in a device pool and takes every stream that has new audio in one *tick*:
+
+    sb = StreamBatch(computer, capacity=4096)        # computer: an STFT frame computer
+    outs = sb.compute_chunks(ids, chunks)             # ids: distinct ints; chunks: 1-D arrays -> list of (k_i, C)
+    outs = sb.finalize(ids)                           # the last frames; the streams are reset and may be reused
+    feats, rows = sb.compute_chunks_packed(ids, d_samples, lengths)   # GPU in, GPU out
+    sb.close()
+
+Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
+the same chunks: the same row counts, dtype and -- for float32 and float64 samples -- the same values bit for bit as
+the computer's plain path (``config.HOST_FEED = False``).  Which streams a tick names, and in which order, changes no
+stream's result.
+
+A tick: the per-stream integer state (:class:`StreamState`: carry length, carry pad, pending skip, first-frame and
+started flags) is advanced on the host with numpy, which fixes every output size without reading the device; samples
+and metadata go up in one copy from pinned memory; ``pds_multistream_assemble_*`` (``csrc/multistream.hip``) writes
+the tick's packed work buffer (carry + chunk of every stream) and the new carries in one launch; the STFT batch
+kernels run over the work buffer with explicit per-stream frame counts, one launch per distinct carry pad (the left
+reflection is launch-wide; in steady state every stream has pad 0); features come down in one copy.  ``finalize``
+reads the carries where they lie in the pool.
+
+Not thread-safe; works on the current torch stream of the device that was current at construction.
+"""
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+from . import _native, config
+from .compute import PackedLayout, ShortTimeFourierTransformFrameComputer
+
+__all__ = ["StreamBatch", "StreamState"]
+
+_FIELDS = 8  # int64 per entry of pds_multistream_assemble's metadata (include/pds_amd.h)
+
+
+def _exclusive_cumsum(x: np.ndarray) -> np.ndarray:
+    out = np.zeros(len(x) + 1, dtype=np.int64)
+    np.cumsum(x, out=out[1:])
+    return out
+
+
+class StreamState:
+    """Host bookkeeping of many streams: the state machine of ``compute_chunk`` / ``finalize`` (compute.py) applied to
+    arrays of streams.  Needs no device.
+
+    Per stream: ``carry_len`` samples carried (always < `frame_length`), ``carry_pad`` left reflection the carry's
+    first frame still needs, ``skip`` samples still to drop (`frame_shift` > `frame_length`), ``first`` no frame
+    emitted yet, ``started`` between the first chunk and ``finalize``, ``half`` the pool half holding the carry.
+    """
+
+    def __init__(self, capacity: int, frame_length: int, frame_shift: int, pad_left: int):
+        capacity = int(capacity)
+        if capacity <= 0:
+            raise ValueError("capacity must be positive")
+        self.capacity = capacity
+        self.L, self.S, self.pad_left = int(frame_length), int(frame_shift), int(pad_left)
+        self.carry_len = np.zeros(capacity, dtype=np.int64)
+        self.carry_pad = np.full(capacity, self.pad_left, dtype=np.int64)
+        self.skip = np.zeros(capacity, dtype=np.int64)
+        self.first = np.ones(capacity, dtype=bool)
+        self.started = np.zeros(capacity, dtype=bool)
+        self.half = np.zeros(capacity, dtype=np.int64)
+
+    def check_ids(self, ids) -> np.ndarray:
+        """`ids` as int64, or ``ValueError`` if any is unknown, negative or repeated"""
+        arr = np.asarray(ids)
+        if arr.ndim != 1:
+            raise ValueError("ids must be a 1-D sequence of stream indices")
+        if arr.size == 0:
+            return np.zeros(0, dtype=np.int64)
+        if not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError("stream ids must be integers")
+        arr = arr.astype(np.int64, copy=False)
+        if arr.min() < 0 or arr.max() >= self.capacity:
+            raise ValueError(f"stream ids must lie in [0, {self.capacity})")
+        if np.unique(arr).size != arr.size:
+            raise ValueError("a tick names each stream at most once")
+        return arr
+
+    def chunk_step(self, ids: np.ndarray, lengths: np.ndarray) -> dict:
+        """What ``compute_chunk`` of chunks of `lengths` does to streams `ids` (compute.py ``compute_chunk``), without
+        changing the state: per stream the samples `drop`ped from the chunk's start, the carry (`carry_len`, `cp`),
+        the work span `avail` = carry + kept chunk, its frame count `k`, where the new carry starts in the span
+        (`new_carry`) and the new state (``commit_chunks`` applies it)"""
+        L, S = self.L, self.S
+        lengths = np.asarray(lengths, dtype=np.int64)
+        skip = self.skip[ids]
+        drop = np.minimum(skip, lengths)
+        skip = skip - drop
+        c, cp = self.carry_len[ids], self.carry_pad[ids]
+        avail = c + lengths - drop
+        k = np.maximum(0, (avail + cp - L) // S + 1)
+        nxt = k * S - cp  # start of the next frame inside the span
+        emit = k > 0
+        fwd = emit & (nxt >= 0)
+        new_carry = np.where(fwd, np.minimum(nxt, avail), 0)
+        step = dict(
+            drop=drop, carry_len=c, cp=cp, avail=avail, k=k, new_carry=new_carry,
+            next_skip=np.where(fwd, np.maximum(0, nxt - avail), skip),
+            next_cp=np.where(fwd, 0, np.where(emit, -nxt, cp)),
+            next_first=self.first[ids] & ~emit,
+            next_carry_len=avail - new_carry,
+        )
+        assert (step["next_carry_len"] < L).all()
+        return step
+
+    def commit_chunks(self, ids: np.ndarray, step: dict) -> None:
+        self.skip[ids] = step["next_skip"]
+        self.carry_pad[ids] = step["next_cp"]
+        self.first[ids] = step["next_first"]
+        self.carry_len[ids] = step["next_carry_len"]
+        self.started[ids] = True
+        self.half[ids] ^= 1  # (the assemble kernel wrote the new carries to the other half)
+
+    def finalize_step(self, ids: np.ndarray) -> dict:
+        """What ``finalize`` does (compute.py ``finalize``): frames `k` from the carry (`carry_len`, left pad `cp`)"""
+        S = self.S
+        c, cp = self.carry_len[ids], self.carry_pad[ids]
+        # (a stream that has not emitted a frame still has carry_pad == pad_left)
+        num = np.where(self.first[ids], (c + S // 2) // S, (c + cp + S // 2 - self.pad_left) // S)
+        k = np.where((num >= 1) & (c > 0), num, 0).astype(np.int64)
+        return dict(carry_len=c, cp=cp, k=k, half=self.half[ids])
+
+    def reset(self, ids: np.ndarray) -> None:
+        self.carry_len[ids] = 0
+        self.carry_pad[ids] = self.pad_left
+        self.skip[ids] = 0
+        self.first[ids] = True
+        self.started[ids] = False
+
+
+class StreamBatch:
+    """``compute_chunk`` / ``finalize`` of many streams of one STFT computer, one tick per call
+
+    `computer`: a :class:`ShortTimeFourierTransformFrameComputer` (its plan and configuration are used; its own
+    streaming state is not touched).  `capacity`: number of streams, ids ``0 .. capacity - 1``.  `dtype`: sample type,
+    float32 or float64, fixed here; chunks of another dtype are converted with numpy's rules and the features have this
+    dtype.  Device memory: the carry pool, ``2 * capacity * frame_length`` samples.
+
+    Under ``config.FLOAT64_ARITHMETIC == "float32"`` float64 samples are rounded to float32 once in the work buffer and
+    the float32 features widened (within the float32 tolerance of the computer's path, not bit for bit).
+    """
+
+    def __init__(self, computer, capacity: int = 4096, dtype=np.float32):
+        if not isinstance(computer, ShortTimeFourierTransformFrameComputer):
+            raise TypeError("StreamBatch serves STFT frame computers (streaming short integration is not supported)")
+        dtype = np.dtype(dtype)
+        if dtype not in (np.float32, np.float64):
+            raise TypeError("StreamBatch: samples must be float32 or float64")
+        torch = _native.require_device()
+        self._torch = torch
+        self._lib = _native.lib()
+        self.dtype = dtype
+        self.state = StreamState(capacity, computer.frame_length, computer.frame_shift, computer.pad_left)
+        self.capacity = self.state.capacity
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.num_coeffs = computer.num_coeffs
+        self._comp = computer
+        self._plan = computer._native_plan(self.device)
+        self._tdtype = torch.float32 if dtype == np.float32 else torch.float64
+        self._assemble = (self._lib.pds_multistream_assemble_f32 if dtype == np.float32
+                          else self._lib.pds_multistream_assemble_f64)
+        self._tile = int(self._lib.pds_multistream_tile())
+        L = computer.frame_length
+        self._pool = torch.zeros((2, self.capacity, L), dtype=self._tdtype, device=self.device)
+        # pinned upload buffers (int64 words: samples, then metadata), used in turn; the event of a buffer's last
+        # copy is waited for before it is written again
+        self._up = [None, None]
+        self._up_events = [None, None]
+        self._up_next = 0
+        self._down = None  # pinned features of the host-array calls
+
+    # ---- public interface -----------------------------------------------------------
+
+    def started(self, ids) -> np.ndarray:
+        """bool per stream of `ids`: between its first chunk and its ``finalize``"""
+        self._check_open()
+        return self.state.started[self.state.check_ids(ids)].copy()
+
+    def compute_chunks(self, ids, chunks: Sequence) -> List[np.ndarray]:
+        """``compute_chunk`` of ``chunks[i]`` (1-D host array) for stream ``ids[i]``; returns the list of feature
+        matrices in the order of `ids`"""
+        self._check_open()
+        ids = self.state.check_ids(ids)
+        if len(chunks) != len(ids):
+            raise ValueError("one chunk per stream id")
+        arrs = [np.asarray(c) for c in chunks]
+        if any(a.ndim != 1 for a in arrs):
+            raise ValueError("chunks must be 1-dimensional")
+        lengths = np.fromiter(map(len, arrs), dtype=np.int64, count=len(arrs))
+        feats, rows = self._chunks_tick(ids, lengths, host_chunks=arrs)
+        return self._to_host(feats, rows, np.ones(len(ids), dtype=bool))
+
+    def compute_chunks_packed(self, ids, d_samples, lengths) -> Tuple[object, np.ndarray]:
+        """``compute_chunk`` of chunks already on the GPU: `d_samples` holds them back to back (1-D contiguous tensor of
+        this object's dtype on its device), ``lengths[i]`` samples for stream ``ids[i]``.  Returns ``(feats, rows)``:
+        the ``(R, num_coeffs)`` GPU tensor and the host int64 ``len(ids) + 1`` row offsets of the streams in it"""
+        self._check_open()
+        torch = self._torch
+        ids = self.state.check_ids(ids)
+        lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        if len(lengths) != len(ids):
+            raise ValueError("one length per stream id")
+        if len(lengths) and lengths.min() < 0:
+            raise ValueError("negative chunk length")
+        if (not isinstance(d_samples, torch.Tensor) or d_samples.device != self.device or d_samples.dim() != 1
+                or not d_samples.is_contiguous() or d_samples.dtype != self._tdtype):
+            raise ValueError(f"d_samples must be a contiguous 1-D {self.dtype} tensor on {self.device}")
+        if int(lengths.sum()) > d_samples.numel():
+            raise ValueError("the chunks lie outside d_samples")
+        return self._chunks_tick(ids, lengths, d_samples=d_samples)
+
+    def finalize(self, ids) -> List[np.ndarray]:
+        """``finalize`` of streams `ids`: their last frames; the streams are reset and may be used again.  A stream
+        that was not started gives ``(0, num_coeffs)`` float64 rows, as ``computer.finalize()`` does"""
+        self._check_open()
+        ids = self.state.check_ids(ids)
+        started = self.state.started[ids].copy()
+        feats, rows = self._finalize_tick(ids)
+        return self._to_host(feats, rows, started)
+
+    def finalize_packed(self, ids) -> Tuple[object, np.ndarray]:
+        """:func:`finalize` with the features left on the GPU: ``(feats, rows)`` as :func:`compute_chunks_packed`"""
+        self._check_open()
+        return self._finalize_tick(self.state.check_ids(ids))
+
+    def close(self) -> None:
+        """Release the pool and the pinned buffers; the object cannot be used afterwards"""
+        self._pool = None
+        self._up = [None, None]
+        self._up_events = [None, None]
+        self._down = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ---- a tick ---------------------------------------------------------------------
+
+    def _check_open(self):
+        if self._pool is None:
+            raise ValueError("StreamBatch is closed")
+
+    def _staging(self, words: int):
+        """the next pinned upload buffer (int64 numpy view of at least `words`), free to write"""
+        torch = self._torch
+        slot = self._up_next
+        self._up_next ^= 1
+        if self._up_events[slot] is not None:
+            self._up_events[slot].synchronize()
+        buf = self._up[slot]
+        if buf is None or buf.numel() < words:
+            size = 1 << 12
+            while size < words:
+                size <<= 1
+            buf = self._up[slot] = torch.empty(size, dtype=torch.int64, pin_memory=True)
+        return slot, buf
+
+    def _send(self, slot: int, words: int):
+        """one copy of the first `words` of upload buffer `slot` to the device, on the current stream"""
+        torch = self._torch
+        dev = torch.empty(max(words, 1), dtype=torch.int64, device=self.device)
+        if words:
+            dev[:words].copy_(self._up[slot][:words], non_blocking=True)
+            ev = self._up_events[slot] = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+        return dev
+
+    def _launch_groups(self, signal, d_lm, order, cp, k, offsets, lengths, row_off, R):
+        """the STFT batch launches of one tick: streams `order` (sorted by carry pad), one launch per distinct pad;
+        `d_lm` is the device int64[4, len(order)] of their offsets, lengths, frame counts and rows"""
+        torch = self._torch
+        C = self.num_coeffs
+        f32_arith = self.dtype == np.float64 and config.FLOAT64_ARITHMETIC == "float32"
+        if f32_arith:
+            signal = signal.to(torch.float32)
+        feats = torch.empty((R, C), dtype=torch.float32 if f32_arith else self._tdtype, device=self.device)
+        if len(order):
+            pads = cp[order]
+            cuts = np.flatnonzero(np.diff(pads)) + 1
+            for lo, hi in zip(np.concatenate([[0], cuts]), np.concatenate([cuts, [len(order)]])):
+                sel = order[lo:hi]
+                # (rows go to the tick's order through d_meta[3]; host row_offsets only bound the output)
+                layout = PackedLayout(B=int(hi - lo), extent=int((offsets[sel] + lengths[sel]).max()),
+                                      nframes=k[sel], row_offsets=np.append(row_off[sel], R), d_meta=d_lm[:, lo:hi])
+                self._comp.launch(signal, layout, out=feats, pad_left=int(pads[lo]))
+        return feats.to(self._tdtype) if f32_arith else feats
+
+    def _chunks_tick(self, ids, lengths, host_chunks=None, d_samples=None):
+        torch = self._torch
+        st = self.state
+        step = st.chunk_step(ids, lengths)
+        n = len(ids)
+        avail, k, cp = step["avail"], step["k"], step["cp"]
+        work_off = _exclusive_cumsum(avail)
+        rows = _exclusive_cumsum(k)
+        R = int(rows[-1])
+        tile_prefix = _exclusive_cumsum((avail + self._tile - 1) // self._tile)
+        emit = np.flatnonzero(k > 0)
+        order = emit[np.argsort(cp[emit], kind="stable")]
+        E = len(order)
+        # upload: [samples][assemble metadata n x 8][tile prefix n + 1][launch metadata 4 x E], int64 words
+        total = int(lengths.sum())
+        ns = (total * self.dtype.itemsize + 7) // 8 if host_chunks is not None else 0
+        words = ns + _FIELDS * n + (n + 1) + 4 * E
+        slot, buf = self._staging(words)
+        host = buf.numpy()
+        if ns and total:
+            np.concatenate(host_chunks, out=host[:ns].view(self.dtype)[:total], casting="unsafe")
+        am = host[ns : ns + _FIELDS * n].reshape(n, _FIELDS)
+        am[:, 0] = ids
+        am[:, 1] = _exclusive_cumsum(lengths)[:-1]
+        am[:, 2] = lengths
+        am[:, 3] = step["carry_len"]
+        am[:, 4] = step["drop"]
+        am[:, 5] = step["new_carry"]
+        am[:, 6] = work_off[:-1]
+        am[:, 7] = st.half[ids]
+        at = ns + _FIELDS * n
+        host[at : at + n + 1] = tile_prefix
+        lm = host[at + n + 1 : words].reshape(4, E)
+        lm[0], lm[1], lm[2], lm[3] = work_off[:-1][order], avail[order], k[order], rows[:-1][order]
+        dev = self._send(slot, words)
+        samples = dev[:ns].view(self._tdtype) if host_chunks is not None else d_samples
+        work = torch.empty(max(int(work_off[-1]), 1), dtype=self._tdtype, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._assemble(samples.data_ptr() if total else None, self._pool.data_ptr(), self.capacity,
+                            st.L, dev[ns:].data_ptr(), dev[at:].data_ptr(), n, int(tile_prefix[-1]),
+                            work.data_ptr(), stream)
+        _native.check(rc, "pds_multistream_assemble")
+        feats = self._launch_groups(work, dev[at + n + 1 : words].view(4, E), order, cp, k, work_off[:-1], avail,
+                                    rows[:-1], R)
+        st.commit_chunks(ids, step)
+        return feats, rows
+
+    def _finalize_tick(self, ids):
+        st = self.state
+        step = st.finalize_step(ids)
+        c, cp, k = step["carry_len"], step["cp"], step["k"]
+        rows = _exclusive_cumsum(k)
+        R = int(rows[-1])
+        offsets = (step["half"] * self.capacity + ids) * st.L  # the carries where they lie in the pool
+        emit = np.flatnonzero(k > 0)
+        order = emit[np.argsort(cp[emit], kind="stable")]
+        E = len(order)
+        slot, buf = self._staging(4 * E)
+        lm = buf.numpy()[: 4 * E].reshape(4, E)
+        lm[0], lm[1], lm[2], lm[3] = offsets[order], c[order], k[order], rows[:-1][order]
+        dev = self._send(slot, 4 * E)
+        feats = self._launch_groups(self._pool.view(-1), dev[: 4 * E].view(4, E), order, cp, k, offsets, c,
+                                    rows[:-1], R)
+        st.reset(ids)
+        return feats, rows
+
+    def _to_host(self, feats, rows, started) -> List[np.ndarray]:
+        """one download into pinned memory, one synchronisation, views per stream"""
+        torch = self._torch
+        R, C = feats.shape
+        if R:
+            if self._down is None or self._down.numel() < R * C:
+                size = 1 << 16
+                while size < R * C:
+                    size <<= 1
+                self._down = torch.empty(size, dtype=self._tdtype, pin_memory=True)
+            pinned = self._down[: R * C].view(R, C)
+            pinned.copy_(feats, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+            host = pinned.numpy().copy()
+        else:
+            host = np.empty((0, C), dtype=self.dtype)
+        idle = np.empty((0, C), dtype=np.float64)
+        return [host[a:b] if s else idle.copy() for a, b, s in zip(rows[:-1].tolist(), rows[1:].tolist(), started)]

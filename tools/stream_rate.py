@@ -1,0 +1,109 @@
+#!/usr/bin/env python3
+"""Per-tick wall time of batched streaming (multistream.StreamBatch) against a loop of single-stream compute_chunk calls.
+
+    python tools/stream_rate.py [--streams 64,1024,8192] [--ticks 200] [--loop 64,256] > profiles/<tag>_stream_rate.txt
+
+Configuration c1_readme_fbank of tests/golden/configs.json (16 kHz, 25 ms frames, 10 ms shift), 160-sample (10 ms)
+float32 chunks.  Per stream count S: `ticks` timed ticks after 20 untimed ones, each ending in a synchronisation --
+compute_chunks (host arrays in, host arrays out) and compute_chunks_packed (samples already on the GPU, features left
+there).  Real-time headroom = chunk duration / p50 tick.  The loop: compute_chunk of one chunk on each of S
+single-stream computers per tick (the host feed path, as a caller gets it).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def pct(xs, q):
+    return float(np.percentile(np.asarray(xs) * 1e3, q))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", default="64,1024,8192")
+    ap.add_argument("--ticks", type=int, default=200)
+    ap.add_argument("--loop", default="64,256")
+    ap.add_argument("--loop-ticks", type=int, default=20)
+    args = ap.parse_args()
+    import torch
+
+    import pydrobert_speech_amd as ps
+    from pydrobert_speech_amd.alias import alias_factory_subclass_from_arg
+    from pydrobert_speech_amd.multistream import StreamBatch
+
+    with open(os.path.join(ROOT, "tests", "golden", "configs.json")) as fh:
+        cfg = json.load(fh)["configs"]["c1_readme_fbank"]
+
+    def computer():
+        return alias_factory_subclass_from_arg(ps.compute.FrameComputer, json.loads(json.dumps(cfg)))
+
+    n = 160
+    chunk_ms = 1e3 * n / 16000
+    rng = np.random.default_rng(0)
+    results = {"config": "c1_readme_fbank", "chunk_samples": n, "device": torch.cuda.get_device_name(0)}
+    warm = 20
+    print(f"# {results['device']}, c1_readme_fbank, {n}-sample chunks ({chunk_ms:.0f} ms), {args.ticks} ticks")
+    print(f"{'streams':>8} {'api':>8} {'p50 ms':>8} {'p99 ms':>8} {'x real time':>12} {'frames/tick':>11}")
+    for S in [int(s) for s in args.streams.split(",")]:
+        comp = computer()
+        block = (3000 * rng.standard_normal((S, n))).astype(np.float32)
+        chunks = list(block)
+        ids = np.arange(S)
+        d_block = torch.from_numpy(block.reshape(-1)).cuda()
+        lens = np.full(S, n, dtype=np.int64)
+        for api in ("host", "packed"):
+            sb = StreamBatch(comp, capacity=S)
+            times, frames = [], 0
+            for t in range(warm + args.ticks):
+                t0 = time.perf_counter()
+                if api == "host":
+                    outs = sb.compute_chunks(ids, chunks)
+                    rows = sum(len(o) for o in outs)
+                else:
+                    feats, r = sb.compute_chunks_packed(ids, d_block, lens)
+                    torch.cuda.current_stream().synchronize()
+                    rows = int(r[-1])
+                t1 = time.perf_counter()
+                if t >= warm:
+                    times.append(t1 - t0)
+                    frames += rows
+            sb.close()
+            p50, p99 = pct(times, 50), pct(times, 99)
+            results[f"{api}_{S}"] = dict(p50_ms=p50, p99_ms=p99, realtime_x=chunk_ms / p50, frames_per_tick=frames / args.ticks)
+            print(f"{S:>8} {api:>8} {p50:>8.3f} {p99:>8.3f} {chunk_ms / p50:>12.1f} {frames / args.ticks:>11.1f}")
+    for S in [int(s) for s in args.loop.split(",")]:
+        comps = [computer() for _ in range(S)]
+        block = (3000 * rng.standard_normal((S, n))).astype(np.float32)
+        times = []
+        for t in range(5 + args.loop_ticks):
+            t0 = time.perf_counter()
+            for c, x in zip(comps, block):
+                c.compute_chunk(x)
+            t1 = time.perf_counter()
+            if t >= 5:
+                times.append(t1 - t0)
+        p50, p99 = pct(times, 50), pct(times, 99)
+        results[f"loop_{S}"] = dict(p50_ms=p50, p99_ms=p99, realtime_x=chunk_ms / p50)
+        print(f"{S:>8} {'loop':>8} {p50:>8.3f} {p99:>8.3f} {chunk_ms / p50:>12.1f}")
+        if f"host_{S}" in results or S == 256:
+            per_stream = p50 / S
+            print(f"#   loop: {1e3 * per_stream:.1f} us per compute_chunk call")
+            results[f"loop_{S}"]["us_per_call"] = 1e3 * per_stream
+    if "host_1024" in results and "loop_256" in results:
+        loop_1024 = results["loop_256"]["us_per_call"] * 1024 / 1e3
+        results["speedup_1024_host_vs_loop"] = loop_1024 / results["host_1024"]["p50_ms"]
+        results["speedup_1024_packed_vs_loop"] = loop_1024 / results["packed_1024"]["p50_ms"]
+        print(f"# 1024 streams: loop (extrapolated from 256, {loop_1024:.2f} ms) / tick: host "
+              f"{results['speedup_1024_host_vs_loop']:.1f} x, packed {results['speedup_1024_packed_vs_loop']:.1f} x")
+    print(json.dumps(results))
+
+
+if __name__ == "__main__":
+    main()
