@@ -136,6 +136,13 @@ __device__ __forceinline__ float fast_log(float x) {
   return __builtin_amdgcn_logf(x) * 0.69314718055994530942f;
 }
 
+// log(max(v, floor)) as Python evaluates it (compute.py:459): a NaN stays a NaN, and -0 and +0 both give the floor.
+// The IEEE maximum propagates NaN the same way and is one v_maximum3_f32 that reads the floor from its SGPR (the select
+// `floor > v ? floor : v` took a broadcast, a compare and a v_cndmask: a VOP3 select cannot read the SGPR and vcc both)
+__device__ __forceinline__ float floor_log(float v, float floor) {
+  return fast_log(__builtin_elementwise_maximum(v, floor));
+}
+
 // Load through the constant address space: tables and utterance records are never written by
 // this kernel, and a uniform address then always becomes a scalar load (the compiler otherwise
 // falls back to 64-lane vector loads wherever it cannot prove that no store precedes the load).
@@ -387,9 +394,22 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
       for (int i = threadIdx.x; i < p.waves * 2 * p.stat_cs; i += p.waves * 64) z[i] = 0.0;
     }
   }
-  // (slots beyond the table read as "no filter": the unrolled slot loop fetches USLOTS entries)
-  for (int i = threadIdx.x; i < p.ell_meta_pad; i += nthreads)
-    meta_lds[i] = i < p.ell_meta_ints ? p.ell_meta[i] : 0;
+  if constexpr (RSG) {
+    // the row-segment walk's records, decoded once per workgroup instead of once per item and round: (byte offset of the
+    // segment's first bin in the power rows, the run flags m1 / m2 as 0 / 1 floats, byte offset of the filter's output
+    // column in a row, or -1 on lanes without a filter).  The launcher sizes meta_pad for them: four ints per entry.
+    int4 *rec_lds = reinterpret_cast<int4 *>(meta_lds);
+    for (int i = threadIdx.x; i < p.seg_rounds * 64; i += nthreads) {
+      const int m = p.ell_meta[i], f = (m >> 16) - 1;
+      rec_lds[i] = make_int4((m & 0x3fff) * 16, __float_as_int((m & (1 << 14)) ? 1.0f : 0.0f),
+                             __float_as_int((m & (1 << 15)) ? 1.0f : 0.0f),
+                             f >= 0 ? ((p.include_energy ? 1 : 0) + f) * (int)sizeof(TOUT) : -1);
+    }
+  } else {
+    // (slots beyond the table read as "no filter": the unrolled slot loop fetches USLOTS entries)
+    for (int i = threadIdx.x; i < p.ell_meta_pad; i += nthreads)
+      meta_lds[i] = i < p.ell_meta_ints ? p.ell_meta[i] : 0;
+  }
   // (16 bytes per thread and pass: every table is a multiple of four floats long and starts on 16 bytes, and
   // so do the wave areas -- a launch's prologue is ~10 us of its ~270, and a pass of this loop a trip to L2)
 #if PDS_FAST_PROLOGUE
@@ -609,8 +629,8 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
     for (int rd = 0; rd < DR; ++rd) {
       if (rd >= p.seg_rounds) break;
       // the lane's column: its filter (first lane of a run), the energy (dl_eslot), or none: a dump slot
-      const int f = (meta_lds[rd * 64 + lane] >> 16) - 1;
-      const int col = f >= 0 ? col0 + f : (p.dl_eslot == rd * 64 + lane ? 0 : -1);
+      const int cb = reinterpret_cast<const int4 *>(meta_lds)[rd * 64 + lane].w;  // (column bytes, float32 features)
+      const int col = cb >= 0 ? cb >> 2 : (p.dl_eslot == rd * 64 + lane ? 0 : -1);
       const float v[12] = {Wp[rd][0], Wp[rd][1], Wp[rd][2], Wp[rd][3], Wc[rd][0], Wc[rd][1],
                            Wc[rd][2], Wc[rd][3], nx[rd][0], nx[rd][1], nx[rd][2], nx[rd][3]};
       float *mine = stage + (col >= 0 ? col : 4 * WS + lane);
@@ -1584,8 +1604,12 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
       }
       float e = energy * p.inv_L;
       if (!use_power) e = __builtin_amdgcn_sqrtf(e);
-      if (p.use_log) e = fast_log(p.log_floor > e ? p.log_floor : e);
-      if (DLT == 0 && valid && r == 0) obase[lane_off - col0] = (TOUT)e;
+      if (p.use_log) e = floor_log(e, p.log_floor);
+      if (DLT == 0 && valid && r == 0) {
+        unsigned off = (lane_off - col0) * (unsigned)sizeof(TOUT);  // (saddr form: see the row-segment walk's stores)
+        asm("" : "+v"(off));
+        *reinterpret_cast<TOUT *>(reinterpret_cast<char *>(obase) + off) = (TOUT)e;
+      }
       if constexpr (DLT > 0) e_keep = e;
       if constexpr (STATS) {
         if (stats_on) {
@@ -1678,8 +1702,7 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
       }
       if (steps & 1u) step();
       float acc = (acc0 + acc1) + (acc2 + acc3);
-      // max(val, floor) as Python evaluates it: a NaN stays a NaN (compute.py:459)
-      if (p.use_log) acc = fast_log(p.log_floor > acc ? p.log_floor : acc);
+      if (p.use_log) acc = floor_log(acc, p.log_floor);
       if constexpr (PDS_ABLATE & 64) {
         keep_alive(acc);
       } else {
@@ -1694,9 +1717,14 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
       // four frames; weights [round][seg_len / 4][lane] float4, powers bin-major.
       const float4 *P4 = reinterpret_cast<const float4 *>(wbase);
       const int t4n = p.seg_len >> 2;
+      // the item's output rows: a wave-uniform base (scalar registers) plus the lane's 32-bit column offset, so the
+      // stores take the global_store_dword voffset, vdata, saddr form; the next frame's row is a scalar add away
+      char *const orow0 = reinterpret_cast<char *>(obase);
+      const int64_t row_bytes = p.out_stride * (int64_t)sizeof(TOUT);
       auto round_body = [&](const int rd, float (&logged)[4]) {
-        const int meta = meta_lds[rd * 64 + lane];
-        const float4 *prow = P4 + (meta & 0x3fff);
+        // the lane's walk record, decoded in the prologue: one 16-byte LDS read
+        const int4 rec = reinterpret_cast<const int4 *>(meta_lds)[rd * 64 + lane];
+        const float4 *prow = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(P4) + rec.x);
         const float4 *wrow = reinterpret_cast<const float4 *>(ellw_lds) + __mul24(rd, t4n) * 64 + lane;
         float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
         auto quad = [&](int t4) {
@@ -1738,7 +1766,7 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
 #endif
         // add up a filter's segments (at most four, on consecutive lanes of one DPP row): lane i takes
         // lane i + 1's sums where the table says the run continues, then lane i + 2's
-        const float m1 = (meta & (1 << 14)) ? 1.0f : 0.0f, m2 = (meta & (1 << 15)) ? 1.0f : 0.0f;
+        const float m1 = __int_as_float(rec.y), m2 = __int_as_float(rec.z);
         auto shl = [](float v, auto ctrl) {
           return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), decltype(ctrl)::value, 0xf, 0xf, true));
         };
@@ -1767,19 +1795,30 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
         a2 = fmaf(shl(a2, inl::Int<0x102>{}), m2, a2);
         a3 = fmaf(shl(a3, inl::Int<0x102>{}), m2, a3);
 #endif
-        const int f = (meta >> 16) - 1;  // the filter, on the first lane of its run; -1 elsewhere
+        // the filter's column (bytes), on the first lane of its run; < 0 elsewhere
+        const int coff = rec.w;
         const float vals[4] = {a0, a1, a2, a3};
-        TOUT *dst = obase + col0 + (f < 0 ? 0 : f);
-#pragma unroll
-        for (int gg = 0; gg < 4; ++gg) {
-          float v = vals[gg];
-          // max(val, floor) as Python evaluates it: a NaN stays a NaN (compute.py:459)
-          if (p.use_log) v = fast_log(p.log_floor > v ? p.log_floor : v);
-          if (DLT == 0 && f >= 0 && gg < frames_here) dst[(int64_t)gg * p.out_stride] = (TOUT)v;
+        // (the empty asm keeps the widening of the offset next to each store: hoisted out of the branches as one 64-bit
+        // value it no longer matches the saddr form, and every store pays a 64-bit vector add.  One variable for all four
+        // stores, so that the register allocator has no copies to make)
+        unsigned off = (unsigned)coff;
+        auto put = [&](const int gg, const float v) {
+          if (DLT == 0 && coff >= 0 && gg < frames_here) {
+            asm("" : "+v"(off));
+            *reinterpret_cast<TOUT *>(orow0 + gg * row_bytes + off) = (TOUT)v;
+          }
           logged[gg] = v;
+        };
+        // (use_log is uniform: a branch around the whole tail, with the stores in both arms, instead of a select per value)
+        if (p.use_log) {
+#pragma unroll
+          for (int gg = 0; gg < 4; ++gg) put(gg, floor_log(vals[gg], p.log_floor));
+        } else {
+#pragma unroll
+          for (int gg = 0; gg < 4; ++gg) put(gg, vals[gg]);
         }
         if constexpr (STATS) {
-          if (stats_on && f >= 0) stat_add4(col0 + f, logged, frames_here);
+          if (stats_on && coff >= 0) stat_add4(coff / (int)sizeof(TOUT), logged, frames_here);
         }
       };
       if constexpr (DLT == 0) {
@@ -2004,8 +2043,7 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
 #pragma unroll
           for (int gg = 0; gg < G::GROUPS; ++gg) {
             float v = sum[gg];
-            // max(val, floor) as Python evaluates it: a NaN stays a NaN (compute.py:459)
-            if (p.use_log) v = fast_log(p.log_floor > v ? p.log_floor : v);
+            if (p.use_log) v = floor_log(v, p.log_floor);
             if (gg < frames_here) obase[(int64_t)gg * p.out_stride + col0 + f] = (TOUT)v;
             sum[gg] = v;
           }

@@ -131,7 +131,8 @@ int32_t launch_wave(const pds_stft_plan *plan, const BatchArgs &a) {
     // (no segmented variant of the fused pre-emphasis kernel)
     if ((cand == 2 && !dl && ft.rs_rounds == 0) || (cand == 1 && (ft.seg_rounds == 0 || pre || a.in_f64 || a.in_i16))) continue;
     const int meta_ints = cand == 3 ? ft.ms_meta_ints : cand == 2 ? (dl ? ft.rsn_rounds : ft.rs_rounds) * 64 : cand == 1 ? ft.seg_meta_ints : ft.ell_slots * N2;
-    const int meta_pad = (std::max(meta_ints, USLOTS * N2) + 3) / 4 * 4;
+    // (the row-segment walk keeps a 16-byte decoded record per entry in LDS: see the kernel's prologue)
+    const int meta_pad = cand == 2 ? meta_ints * 4 : (std::max(meta_ints, USLOTS * N2) + 3) / 4 * 4;
     const size_t fixed = (size_t)N2 * 8 + (size_t)meta_pad * 4 + (cand == 2 && pf_ok ? pf_extra : 0) + lean_extra +
                          (cand == 3 && MSEG3 ? mseg3_extra : 0);
     const size_t table_bytes = (size_t)(cand == 3 ? ft.ms_wfloats : cand == 2 ? (dl ? ft.rsn_wfloats : ft.rs_wfloats) : cand == 1 ? ft.seg_wfloats : ft.ell_wfloats) * 4;
