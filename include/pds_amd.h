@@ -90,6 +90,11 @@ int64_t pds_stft_num_frames(const pds_stft_plan *plan, int64_t n);
  * LDS/register FFT geometry serves it (128 .. 2048, or an unpadded N = L of 160 .. 960),
  * 0 = generic kernels (radix-2 FFT in LDS for powers of two, direct DFT otherwise) */
 int32_t pds_stft_plan_kernel_kind(const pds_stft_plan *plan);
+/* the filter walk a fused plan prefers, bits 0-7 (0 ELL, 1 segments, 2 row segments, 3 matrix-pipe segments; a launch
+ * falls back towards 0 when a walk's tables do not fit in LDS beside its waves' areas or it does not serve the sample
+ * format), and in bits 8-11 which of the four the plan built tables for (bit 8 + id).  -1: no fused kernel.  The
+ * environment's PDS_STFT_WALK = ell | seg | rseg | mseg, read when the plan is created, forces a walk that was built */
+int32_t pds_stft_plan_filter_walk(const pds_stft_plan *plan);
 
 /*
  * Batched compute_full (compute.py:574-607) over B utterances packed in one buffer.

@@ -223,6 +223,10 @@ class _NativePlan:
         _native.check(rc, "pds_stft_plan_create")
         self.handle = handle
         self.kernel_kind = lib.pds_stft_plan_kernel_kind(handle)
+        # the preferred filter walk and the walks the plan built tables for (None, (): no fused kernel)
+        walks, bits = ("ell", "seg", "rseg", "mseg"), lib.pds_stft_plan_filter_walk(handle)
+        self.walk = walks[bits & 255] if bits >= 0 else None
+        self.walks_built = tuple(w for i, w in enumerate(walks) if bits >= 0 and bits >> (8 + i) & 1)
         self.has_f64in = bool(lib.pds_stft_plan_has_f64in(handle))
         self.has_i16in = bool(lib.pds_stft_plan_has_i16in(handle))
         self.has_fused_deltas = bool(lib.pds_stft_plan_has_fused_deltas(handle))

@@ -131,6 +131,11 @@ int64_t pds_stft_num_frames(const pds_stft_plan *p, int64_t n) {
 }
 
 int32_t pds_stft_plan_kernel_kind(const pds_stft_plan *p) { return p ? p->fast.kind : 0; }
+int32_t pds_stft_plan_filter_walk(const pds_stft_plan *p) {
+  if (!p || !p->fast.kind) return -1;
+  const auto &ft = p->fast;
+  return ft.walk | (1 | (ft.seg_rounds > 0) << 1 | (ft.rs_rounds > 0) << 2 | (ft.ms_rounds > 0) << 3) << 8;
+}
 
 static int32_t check_batch(const pds_stft_plan *plan, const void *sig, const int64_t *off,
                            const int64_t *len, const int64_t *nfr, const int64_t *row,

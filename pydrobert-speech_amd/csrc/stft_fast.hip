@@ -135,7 +135,19 @@ int32_t fast_tables_create(pds_stft_plan *plan, const double *window, const int3
   for (int r = 0; r < n2; ++r)
     for (int k = 0; k < n1; ++k) {
       const int idx = n2 * k + r;
-      if (idx < d.frame_length) win[(size_t)r * n1 + k] = (float)window[idx];
+      if (idx < d.frame_length) {
+        // A tap that is exactly 0 INSIDE the frame (the end taps of a Hann or Bartlett window) is stored as 2^-100:
+        // the kernel's window multiply gives 0 * x = 0 for every x, which the lanes past the frame's end need, but
+        // the reference poisons a frame whose NaN / Inf sample sits under such a tap (0 * NaN = NaN).  2^-100 x is
+        // below half an ulp of anything a frame with another sample of x's size sums to (and its square underflows
+        // for |x| < 1e11), a NaN stays a NaN and an Inf an Inf.  (2^-101, the tap of win_half below, is still normal.)
+        // The limit: a frame that is silent except under such a tap gives 2^-100 |x| per bin where the reference gives
+        // exactly 0 -- 2.4e-26 for x = 3e4.  Power features square it away; magnitude features keep it, far below the
+        // default floor of 1e-5 and the tolerances, but above a log floor chosen below ~1e-25 (the fast path takes
+        // floors down to 1.18e-38) and not 0 without a log.
+        const float w = (float)window[idx];
+        win[(size_t)r * n1 + k] = w == 0.0f ? 0x1p-100f : w;
+      }
     }
   std::vector<float> tw((size_t)n2 * cols * 2, 0.0f);
   for (int r = 0; r < n2; ++r)

@@ -57,7 +57,7 @@ struct FastParams {
   const int64_t *offsets, *lengths, *nframes, *row_off;
   void *out;  // TOUT features
   int64_t out_stride;
-  const float *win_lane;    // [N2][N1]   window[N2*n1 + n2], zero beyond L
+  const float *win_lane;    // [N2][N1]   window[N2*n1 + n2], zero beyond L (and only there: zero taps are 2^-100)
   const float2 *tw_lane;    // [N2][N1/2] W_N^(n2*k1), pre-scaled (see rdft_scaled)
   const float2 *tw_special; // [N2] e^{-2 pi i r / (2 N2)}
   const float *win_half;    // PF: [N2][N1] the window times 1/2 (see twiddle_seeds)
@@ -109,7 +109,9 @@ __device__ __forceinline__ float mul_legacy(float x, float y) {
 
 // The window multiply of row n1 of a frame.  Rows below N1 / 2 lie wholly inside the frame (the kernel requires
 // L > N / 2); a row above may hold lanes past the frame's end -- they read samples of the next frame, possibly Inf / NaN,
-// and their window value is exactly 0 -- and takes the 0 * x = 0 multiply.  The ordinary multiplies of the rows below
+// and their window value is exactly 0 -- and takes the 0 * x = 0 multiply.  (A zero tap INSIDE the frame must still let
+// a NaN / Inf sample poison the frame as 0 * NaN does in the reference: the plan stores it as 2^-100, see
+// fast_tables_create.)  The ordinary multiplies of the rows below
 // contract with the transform's first additions, x[n] +- x[n + N1/2]: one multiply and two multiply-adds per pair
 // instead of two and two.
 template <int N1>
