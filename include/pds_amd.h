@@ -341,6 +341,37 @@ int32_t pds_multistream_assemble_f64(const double *d_chunks, double *d_pool, int
                                      int64_t total_tiles, double *d_work, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * Delta features of batched streaming (StreamBatch(deltas=...)): statics + d_1 .. d_K of every stream, delayed by the
+ * look-ahead H = K * context_window frames, bit for bit pds_deltas_* over the stream's whole sequence of statics.  The
+ * last 2 H static rows of `capacity` streams live in a device pool T[2][capacity][hist_rows = 2 H][coeffs], oldest row
+ * first: stream s's history is in half h of its slot, d_hist + ((h * capacity + s) * hist_rows) * coeffs, and a tick
+ * reads one half and writes the other (ping-pong, as the carries above).
+ * pds_multistream_deltas runs once per tick, after the tick's statics have been written to d_statics (rows of `coeffs`
+ * values, by pds_stft_batch_* as above).  d_meta holds n entries of 8 int64:
+ *   [0] stream s   [1] flags: bit 0 half h the history is read from, bit 1 final (the stream's finalize)
+ *   [2] valid history rows v (<= hist_rows)   [3] new static rows k   [4] first of them in d_statics (row index)
+ *   [5] first output row p in the virtual sequence "v history rows, then k new rows" (V = v + k rows)
+ *   [6] output rows m (p + m <= V)   [7] first output row in d_out (row index; rows of (K + 1) * coeffs values)
+ * and, with seq(j) = row min(max(j, 0), V - 1) of that sequence, writes for r < m
+ *   d_out[[7] + r] = [seq(p + r), d_1, .., d_K],  d_k = (T) sum_j filt_k[j] * seq(p + r + j - M_k)  (float64, taps
+ *   ascending, multiply and add rounded separately, from 0.0; filt_k = d_filts[d_filt_off[k - 1] .. d_filt_off[k]),
+ *   M_k = (its length - 1) / 2, as pds_deltas_*)
+ * and, unless final, pool[1 - h][s][q] = seq(V - keep + q) for q < keep = min(V, hist_rows).  The clamp in seq is the
+ * "edge" padding at a stream's start (p + j - M_k < 0 only while row 0 of the sequence is the stream's first frame) and,
+ * with final, at its end; the caller chooses p and m so that it never acts otherwise.  Work is dealt by element:
+ * d_elem_prefix (int64[n + 1]) is the exclusive prefix sum of (m + keep) * coeffs (final: m * coeffs), total_elems its
+ * last element.  Streams of one call are distinct.
+ * --------------------------------------------------------------------------------- */
+int32_t pds_multistream_deltas_f32(const float *d_statics, float *d_hist, int64_t capacity, int32_t hist_rows,
+                                   int32_t coeffs, const double *d_filts, const int32_t *d_filt_off, int32_t K,
+                                   const int64_t *d_meta, const int64_t *d_elem_prefix, int32_t n, int64_t total_elems,
+                                   float *d_out, void *stream);
+int32_t pds_multistream_deltas_f64(const double *d_statics, double *d_hist, int64_t capacity, int32_t hist_rows,
+                                   int32_t coeffs, const double *d_filts, const int32_t *d_filt_off, int32_t K,
+                                   const int64_t *d_meta, const int64_t *d_elem_prefix, int32_t n, int64_t total_elems,
+                                   double *d_out, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Pre-processors as separate passes (reference pre.py:67-149); `preemph` above fuses the
  * first one into the frame load instead.
  * pds_preemphasize: per utterance of a packed buffer (offsets/lengths as in pds_stft_batch),

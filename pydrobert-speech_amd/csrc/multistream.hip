@@ -8,6 +8,15 @@
 // another block of the same stream writes).  The STFT batch launches then read the work buffer with explicit
 // per-stream frame counts.  Work is dealt in tiles of MS_TILE samples of one stream; `tile_prefix[e]` is the first
 // tile of entry e, so one long chunk spreads over many workgroups and a tick of short ones takes one each.
+//
+// Delta features across ticks (StreamBatch(deltas=...)): multistream_deltas_kernel, after the STFT launches of a tick.
+// Every stream of the tick is one entry of `meta` (int64[n][MD_FIELDS]).  Its virtual sequence is its `valid` history
+// rows (pool half h) followed by its `fresh` new static rows; the entry's output rows are rows first .. first + rows of
+// that sequence with their deltas, every tap's row index clamped to the sequence ("edge" padding at a stream's start
+// and, for an entry with the final flag, at its end), and its next history is the sequence's last keep = min(valid +
+// fresh, hist_rows) rows, written to the other half (final: keep = 0, the stream is reset).  Work is dealt by element:
+// an entry has (rows + keep) * coeffs of them, `elem_prefix` their exclusive prefix sum, and lane g of the grid takes element g -- adjacent lanes hold adjacent coefficients of one row, whether a tick
+// brings thousands of streams one frame each or one stream thousands of frames.
 #include "pds_internal.h"
 
 namespace pds {
@@ -74,6 +83,77 @@ static int32_t launch_assemble(const T *d_chunks, T *d_pool, int64_t capacity, i
   return PDS_OK;
 }
 
+// ---- delta features across ticks ------------------------------------------------------------------------------
+
+enum { MD_STREAM = 0, MD_FLAGS, MD_VALID, MD_FRESH, MD_STATIC_ROW, MD_FIRST, MD_ROWS, MD_OUT_ROW, MD_FIELDS };
+enum { MD_FLAG_HALF = 1, MD_FLAG_FINAL = 2 };
+constexpr int MD_THREADS = 256;
+
+template <typename T>
+__global__ __launch_bounds__(MD_THREADS) void multistream_deltas_kernel(
+    const T *__restrict__ statics, T *hist, int64_t capacity, int32_t hist_rows, int32_t F,
+    const double *__restrict__ filts, const int32_t *__restrict__ filt_off, int32_t K,
+    const int64_t *__restrict__ meta, const int64_t *__restrict__ elem_prefix, int32_t n, int64_t total,
+    T *__restrict__ out) {
+  const int64_t g = (int64_t)blockIdx.x * MD_THREADS + threadIdx.x;
+  if (g >= total) return;
+  // entry of this element: the last e with elem_prefix[e] <= g (entries without elements are passed over)
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (elem_prefix[mid] <= g) lo = mid; else hi = mid;
+  }
+  const int64_t *m = meta + (int64_t)lo * MD_FIELDS;
+  const int64_t s = m[MD_STREAM], half = m[MD_FLAGS] & MD_FLAG_HALF, valid = m[MD_VALID], rows = m[MD_ROWS];
+  const int64_t V = valid + m[MD_FRESH];  // (> 0: an entry with elements has a row to show or to keep)
+  const int64_t slot = (int64_t)hist_rows * F;
+  const T *hin = hist + (half * capacity + s) * slot;
+  const int64_t fresh_at = m[MD_STATIC_ROW] - valid;  // statics row of row v >= valid of the sequence: fresh_at + v
+  const int64_t l = g - elem_prefix[lo];
+  const int64_t r = l / F;
+  const int i = (int)(l - r * F);
+  auto row = [&](int64_t v) -> T {
+    v = v < 0 ? 0 : (v >= V ? V - 1 : v);
+    return v < valid ? hin[v * F + i] : statics[(fresh_at + v) * F + i];
+  };
+  if (r >= rows) {  // a row of the next history: the sequence's last min(V, hist_rows) rows (none after a finalize)
+    if (m[MD_FLAGS] & MD_FLAG_FINAL) return;
+    const int64_t q = r - rows, keep = V < hist_rows ? V : hist_rows;
+    hist[((1 - half) * capacity + s) * slot + q * F + i] = row(V - keep + q);
+    return;
+  }
+  const int64_t p = m[MD_FIRST] + r;
+  T *orow = out + (m[MD_OUT_ROW] + r) * ((int64_t)(K + 1) * F) + i;
+  orow[0] = row(p);
+  for (int k = 1; k <= K; ++k) {
+    const int f0 = filt_off[k - 1], len = filt_off[k] - f0;
+    const int M = (len - 1) / 2;
+    double acc = 0.0;
+    // post.hip's arithmetic: multiply and add rounded separately (the Makefile builds this file without contraction)
+    for (int j = 0; j < len; ++j) acc = __dadd_rn(acc, __dmul_rn(filts[f0 + j], (double)row(p + j - M)));
+    orow[(int64_t)k * F] = (T)acc;
+  }
+}
+
+template <typename T>
+static int32_t launch_ms_deltas(const T *d_statics, T *d_hist, int64_t capacity, int32_t hist_rows, int32_t coeffs,
+                                const double *d_filts, const int32_t *d_filt_off, int32_t K, const int64_t *d_meta,
+                                const int64_t *d_elem_prefix, int32_t n, int64_t total_elems, T *d_out, void *stream) {
+  if (n < 0 || total_elems < 0 || capacity < 0 || hist_rows <= 0 || coeffs <= 0 || K < 1)
+    return invalid_ms("multistream_deltas: bad size");
+  if (n == 0 || total_elems == 0) return PDS_OK;
+  const int64_t blocks = (total_elems + MD_THREADS - 1) / MD_THREADS;
+  if (blocks > 0x7fffffff) return invalid_ms("multistream_deltas: too many elements in one call");
+  // (d_statics / d_out may be null in a tick without new rows / without rows due: only histories move)
+  if (!d_hist || !d_filts || !d_filt_off || !d_meta || !d_elem_prefix)
+    return invalid_ms("multistream_deltas: null pointer");
+  hipLaunchKernelGGL(multistream_deltas_kernel<T>, dim3((unsigned)blocks), dim3(MD_THREADS), 0, (hipStream_t)stream,
+                     d_statics, d_hist, capacity, hist_rows, coeffs, d_filts, d_filt_off, K, d_meta, d_elem_prefix, n,
+                     total_elems, d_out);
+  PDS_HIP(hipGetLastError());
+  return PDS_OK;
+}
+
 }  // namespace pds
 
 extern "C" {
@@ -91,6 +171,21 @@ int32_t pds_multistream_assemble_f64(const double *d_chunks, double *d_pool, int
                                      int64_t total_tiles, double *d_work, void *stream) {
   return pds::launch_assemble<double>(d_chunks, d_pool, capacity, frame_length, d_meta, d_tile_prefix, n, total_tiles,
                                       d_work, stream);
+}
+
+int32_t pds_multistream_deltas_f32(const float *d_statics, float *d_hist, int64_t capacity, int32_t hist_rows,
+                                   int32_t coeffs, const double *d_filts, const int32_t *d_filt_off, int32_t K,
+                                   const int64_t *d_meta, const int64_t *d_elem_prefix, int32_t n, int64_t total_elems,
+                                   float *d_out, void *stream) {
+  return pds::launch_ms_deltas<float>(d_statics, d_hist, capacity, hist_rows, coeffs, d_filts, d_filt_off, K, d_meta,
+                                      d_elem_prefix, n, total_elems, d_out, stream);
+}
+int32_t pds_multistream_deltas_f64(const double *d_statics, double *d_hist, int64_t capacity, int32_t hist_rows,
+                                   int32_t coeffs, const double *d_filts, const int32_t *d_filt_off, int32_t K,
+                                   const int64_t *d_meta, const int64_t *d_elem_prefix, int32_t n, int64_t total_elems,
+                                   double *d_out, void *stream) {
+  return pds::launch_ms_deltas<double>(d_statics, d_hist, capacity, hist_rows, coeffs, d_filts, d_filt_off, K, d_meta,
+                                       d_elem_prefix, n, total_elems, d_out, stream);
 }
 
 }  // extern "C"

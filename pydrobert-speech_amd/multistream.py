@@ -10,6 +10,8 @@ samples of up to `capacity` streams in a device pool and takes every stream that
     feats, rows = sb.compute_chunks_packed(ids, d_samples, lengths)   # GPU in, GPU out
     sb.close()
 
+    sb = StreamBatch(computer, capacity=4096, deltas=Deltas(2))   # statics + delta + delta-delta, see below
+
 Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
 the same chunks: the same row counts, dtype and -- for float32 and float64 samples -- the same values bit for bit as
 the computer's plain path (``config.HOST_FEED = False``).  Which streams a tick names, and in which order, changes no
@@ -23,18 +25,32 @@ kernels run over the work buffer with explicit per-stream frame counts, one laun
 reflection is launch-wide; in steady state every stream has pad 0); features come down in one copy.  ``finalize``
 reads the carries where they lie in the pool.
 
+With `deltas` (a :class:`post.Deltas`: "edge" padding, concatenated along the coefficient axis) a stream's rows are
+those of ``deltas.apply(X, axis=0)`` over the whole sequence X of its statics, bit for bit, delayed by the look-ahead
+``H = num_deltas * context_window`` frames a delta row needs of the future: a ``compute_chunks`` call returns the rows
+whose future has arrived, ``finalize`` the last ones with the right edge replicated.  :class:`DeltaState` counts
+frames and rows per stream on the host; the device keeps every stream's last ``2 H`` static rows in a second
+ping-pong pool, and one launch per tick (``pds_multistream_deltas_*``) reads "history, then the tick's new statics",
+writes the rows due and the next history.  ``2 H`` rows suffice: after a tick the rows not yet returned are the last
+H frames, the first of them reaches H further back, and while a stream has seen at most ``2 H`` frames its frame 0 is
+still in the history, so the left edge replication never needs a row that is gone.
+
 Not thread-safe; works on the current torch stream of the device that was current at construction.
 """
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _native, config
+from .alias import alias_factory_subclass_from_arg
 from .compute import PackedLayout, ShortTimeFourierTransformFrameComputer
+from .post import Deltas, PostProcessor
 
-__all__ = ["StreamBatch", "StreamState"]
+__all__ = ["DeltaState", "StreamBatch", "StreamState", "streaming_deltas"]
 
 _FIELDS = 8  # int64 per entry of pds_multistream_assemble's metadata (include/pds_amd.h)
+_DFIELDS = 8  # ... and of pds_multistream_deltas'
+_FLAG_FINAL = 2  # (bit 0 of the flags word is the pool half)
 
 
 def _exclusive_cumsum(x: np.ndarray) -> np.ndarray:
@@ -133,6 +149,107 @@ class StreamState:
         self.started[ids] = False
 
 
+def streaming_deltas(deltas) -> Optional[Tuple[Deltas, int, int]]:
+    """`deltas` as :class:`StreamBatch` takes it -> ``(Deltas, num_deltas, context_window)``, or None for no deltas
+    (``deltas=None`` or ``num_deltas == 0``); ``ValueError`` for settings batched streaming does not serve"""
+    if deltas is None:
+        return None
+    try:
+        deltas = alias_factory_subclass_from_arg(PostProcessor, deltas)
+    except (KeyError, TypeError) as e:
+        raise ValueError(f"StreamBatch: deltas is no post-processor ({e!r})") from None
+    if not isinstance(deltas, Deltas):
+        raise ValueError("StreamBatch: deltas must be a post.Deltas")
+    K = int(deltas.num_deltas)
+    if K < 0:
+        raise ValueError("StreamBatch: num_deltas must not be negative")
+    if deltas._pad_mode != "edge" or deltas._pad_kwargs:
+        raise ValueError("StreamBatch: deltas must use pad_mode='edge' without pad arguments")
+    if not deltas.concatenate:
+        raise ValueError("StreamBatch: deltas must be concatenated (concatenate=True)")
+    if deltas._target_axis not in (-1, 1):
+        raise ValueError("StreamBatch: the deltas' target axis must be the coefficient axis of (rows, coeffs): -1 or 1")
+    if K == 0:
+        return None
+    W = (len(deltas._filts[1]) - 1) // 2
+    if W < 1:
+        raise ValueError("StreamBatch: context_window must be positive")
+    return deltas, K, W
+
+
+class DeltaState:
+    """Host bookkeeping of the delayed delta rows of many streams.  Needs no device.
+
+    Per stream: ``seen`` static frames produced since its start, ``emitted`` rows returned, ``valid`` rows of its
+    device history (``min(seen, 2 * lookahead)``: the frames ``seen - valid .. seen - 1``, oldest first), ``half`` the
+    pool half holding it.
+    """
+
+    def __init__(self, capacity: int, lookahead: int):
+        capacity, lookahead = int(capacity), int(lookahead)
+        if capacity <= 0 or lookahead <= 0:
+            raise ValueError("capacity and lookahead must be positive")
+        self.capacity, self.H = capacity, lookahead
+        self.hist_rows = 2 * lookahead
+        self.seen = np.zeros(capacity, dtype=np.int64)
+        self.emitted = np.zeros(capacity, dtype=np.int64)
+        self.valid = np.zeros(capacity, dtype=np.int64)
+        self.half = np.zeros(capacity, dtype=np.int64)
+
+    def step(self, ids: np.ndarray, k: np.ndarray, final: bool = False) -> dict:
+        """What a tick that brings streams `ids` `k` new static frames does, without changing the state.  Per stream,
+        over the virtual sequence "`valid` history rows, then `k` new rows": `rows` output rows starting at row `first`
+        of the sequence (all the stream's remaining ones if `final`, else those whose `H` frames of future are there),
+        `keep` rows of next history (the sequence's last ones; none if `final`) and the `half` the history is read
+        from"""
+        H = self.H
+        k = np.asarray(k, dtype=np.int64)
+        seen, emitted, valid = self.seen[ids], self.emitted[ids], self.valid[ids]
+        n, V = seen + k, valid + k
+        rows = n - emitted if final else np.maximum(0, n - H) - emitted
+        first = emitted - (seen - valid)
+        keep = np.zeros_like(V) if final else np.minimum(V, self.hist_rows)
+        # the kernel's clamp of a row index to the sequence is "edge" padding and nothing else: every row a tap reads
+        # is in the sequence, unless it lies before the stream's frame 0 (row 0 of the sequence is then frame 0) or,
+        # in a finalize, after its last frame
+        assert (rows >= 0).all() and (first >= 0).all() and (first + rows <= V).all()
+        assert ((first - H >= 0) | (seen == valid) | (rows == 0)).all()
+        assert final or (first + rows - 1 + H <= V - 1)[rows > 0].all()
+        return dict(valid=valid, k=k, first=first, rows=rows, keep=keep, half=self.half[ids], final=bool(final),
+                    next_seen=n, next_emitted=emitted + rows)
+
+    def commit(self, ids: np.ndarray, step: dict) -> None:
+        if step["final"]:
+            self.reset(ids)
+            return
+        self.seen[ids] = step["next_seen"]
+        self.emitted[ids] = step["next_emitted"]
+        self.valid[ids] = step["keep"]
+        self.half[ids] ^= 1  # (the deltas kernel wrote the next histories to the other half)
+
+    def reset(self, ids: np.ndarray) -> None:
+        self.seen[ids] = 0
+        self.emitted[ids] = 0
+        self.valid[ids] = 0
+
+    def fill_meta(self, meta: np.ndarray, prefix: np.ndarray, ids: np.ndarray, step: dict, static_rows: np.ndarray,
+                  out_rows: np.ndarray, coeffs: int) -> int:
+        """pds_multistream_deltas' metadata of a tick into `meta` (int64[n, 8]) and `prefix` (int64[n + 1], elements
+        per entry as an exclusive prefix sum); `static_rows` / `out_rows`: each stream's first row in the tick's
+        statics and in its output.  Returns the number of elements"""
+        meta[:, 0] = ids
+        meta[:, 1] = step["half"] | (_FLAG_FINAL if step["final"] else 0)
+        meta[:, 2] = step["valid"]
+        meta[:, 3] = step["k"]
+        meta[:, 4] = static_rows
+        meta[:, 5] = step["first"]
+        meta[:, 6] = step["rows"]
+        meta[:, 7] = out_rows
+        prefix[0] = 0
+        np.cumsum((step["rows"] + step["keep"]) * int(coeffs), out=prefix[1:])
+        return int(prefix[-1])
+
+
 class StreamBatch:
     """``compute_chunk`` / ``finalize`` of many streams of one STFT computer, one tick per call
 
@@ -141,16 +258,26 @@ class StreamBatch:
     float32 or float64, fixed here; chunks of another dtype are converted with numpy's rules and the features have this
     dtype.  Device memory: the carry pool, ``2 * capacity * frame_length`` samples.
 
+    `deltas`: a :class:`post.Deltas` (or what ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one) with
+    ``pad_mode="edge"``, ``concatenate=True`` and the coefficient axis as target; ``None`` or ``num_deltas == 0``: no
+    deltas.  With ``F = computer.num_coeffs``, ``K = num_deltas`` and ``H = K * context_window`` (:attr:`lookahead`)
+    every stream's rows become ``[static, d_1 .. d_K]`` (``num_coeffs == (K + 1) * F``), equal bit for bit to
+    ``deltas.apply(X, axis=0)`` of its concatenated statics X and delayed by H frames: when a stream has produced n
+    static frames and been given e rows, a ``compute_chunks`` call returns ``max(0, n - H) - e`` rows and ``finalize``
+    the last ``n - e``.  Additional device memory: the history pool, exactly ``2 * capacity * 2 * H * F`` elements of
+    `dtype` (two halves of ``2 H`` static rows per stream), and per tick the ``(new rows, F)`` statics.
+
     Under ``config.FLOAT64_ARITHMETIC == "float32"`` float64 samples are rounded to float32 once in the work buffer and
     the float32 features widened (within the float32 tolerance of the computer's path, not bit for bit).
     """
 
-    def __init__(self, computer, capacity: int = 4096, dtype=np.float32):
+    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None):
         if not isinstance(computer, ShortTimeFourierTransformFrameComputer):
             raise TypeError("StreamBatch serves STFT frame computers (streaming short integration is not supported)")
         dtype = np.dtype(dtype)
         if dtype not in (np.float32, np.float64):
             raise TypeError("StreamBatch: samples must be float32 or float64")
+        spec = streaming_deltas(deltas)
         torch = _native.require_device()
         self._torch = torch
         self._lib = _native.lib()
@@ -158,7 +285,8 @@ class StreamBatch:
         self.state = StreamState(capacity, computer.frame_length, computer.frame_shift, computer.pad_left)
         self.capacity = self.state.capacity
         self.device = torch.device("cuda", torch.cuda.current_device())
-        self.num_coeffs = computer.num_coeffs
+        self._F = computer.num_coeffs  # statics per row
+        self.num_coeffs = self._F
         self._comp = computer
         self._plan = computer._native_plan(self.device)
         self._tdtype = torch.float32 if dtype == np.float32 else torch.float64
@@ -173,8 +301,23 @@ class StreamBatch:
         self._up_events = [None, None]
         self._up_next = 0
         self._down = None  # pinned features of the host-array calls
+        self.dstate = self._hist = None
+        if spec is not None:
+            self._deltas, self._K, W = spec
+            self.dstate = DeltaState(self.capacity, self._K * W)
+            self.num_coeffs = (self._K + 1) * self._F
+            self._hist = torch.zeros((2, self.capacity, self.dstate.hist_rows, self._F), dtype=self._tdtype,
+                                     device=self.device)
+            self._d_filts, self._d_filt_off = self._deltas._filters_on(self.device)
+            self._deltas_fn = (self._lib.pds_multistream_deltas_f32 if dtype == np.float32
+                               else self._lib.pds_multistream_deltas_f64)
 
     # ---- public interface -----------------------------------------------------------
+
+    @property
+    def lookahead(self) -> int:
+        """frames of delay of the rows: ``num_deltas * context_window`` (0 without deltas)"""
+        return self.dstate.H if self.dstate is not None else 0
 
     def started(self, ids) -> np.ndarray:
         """bool per stream of `ids`: between its first chunk and its ``finalize``"""
@@ -230,7 +373,7 @@ class StreamBatch:
 
     def close(self) -> None:
         """Release the pool and the pinned buffers; the object cannot be used afterwards"""
-        self._pool = None
+        self._pool = self._hist = None
         self._up = [None, None]
         self._up_events = [None, None]
         self._down = None
@@ -276,7 +419,7 @@ class StreamBatch:
         """the STFT batch launches of one tick: streams `order` (sorted by carry pad), one launch per distinct pad;
         `d_lm` is the device int64[4, len(order)] of their offsets, lengths, frame counts and rows"""
         torch = self._torch
-        C = self.num_coeffs
+        C = self._F
         f32_arith = self.dtype == np.float64 and config.FLOAT64_ARITHMETIC == "float32"
         if f32_arith:
             signal = signal.to(torch.float32)
@@ -305,12 +448,16 @@ class StreamBatch:
         emit = np.flatnonzero(k > 0)
         order = emit[np.argsort(cp[emit], kind="stable")]
         E = len(order)
-        # upload: [samples][assemble metadata n x 8][tile prefix n + 1][launch metadata 4 x E], int64 words
+        # upload: [samples][assemble metadata n x 8][tile prefix n + 1][launch metadata 4 x E], int64 words, and with
+        # deltas [deltas metadata n x 8][element prefix n + 1] behind them
         total = int(lengths.sum())
         ns = (total * self.dtype.itemsize + 7) // 8 if host_chunks is not None else 0
         words = ns + _FIELDS * n + (n + 1) + 4 * E
-        slot, buf = self._staging(words)
+        dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
+        slot, buf = self._staging(words + dwords)
         host = buf.numpy()
+        if dwords:
+            dstep, elems = self._delta_meta(host[words : words + dwords], ids, k, rows[:-1], final=False)
         if ns and total:
             np.concatenate(host_chunks, out=host[:ns].view(self.dtype)[:total], casting="unsafe")
         am = host[ns : ns + _FIELDS * n].reshape(n, _FIELDS)
@@ -326,7 +473,7 @@ class StreamBatch:
         host[at : at + n + 1] = tile_prefix
         lm = host[at + n + 1 : words].reshape(4, E)
         lm[0], lm[1], lm[2], lm[3] = work_off[:-1][order], avail[order], k[order], rows[:-1][order]
-        dev = self._send(slot, words)
+        dev = self._send(slot, words + dwords)
         samples = dev[:ns].view(self._tdtype) if host_chunks is not None else d_samples
         work = torch.empty(max(int(work_off[-1]), 1), dtype=self._tdtype, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -337,6 +484,8 @@ class StreamBatch:
         feats = self._launch_groups(work, dev[at + n + 1 : words].view(4, E), order, cp, k, work_off[:-1], avail,
                                     rows[:-1], R)
         st.commit_chunks(ids, step)
+        if dwords:
+            return self._delta_launch(feats, dev[words : words + dwords], ids, dstep, elems)
         return feats, rows
 
     def _finalize_tick(self, ids):
@@ -349,14 +498,43 @@ class StreamBatch:
         emit = np.flatnonzero(k > 0)
         order = emit[np.argsort(cp[emit], kind="stable")]
         E = len(order)
-        slot, buf = self._staging(4 * E)
+        n = len(ids)
+        dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
+        slot, buf = self._staging(4 * E + dwords)
         lm = buf.numpy()[: 4 * E].reshape(4, E)
         lm[0], lm[1], lm[2], lm[3] = offsets[order], c[order], k[order], rows[:-1][order]
-        dev = self._send(slot, 4 * E)
+        if dwords:
+            dstep, elems = self._delta_meta(buf.numpy()[4 * E : 4 * E + dwords], ids, k, rows[:-1], final=True)
+        dev = self._send(slot, 4 * E + dwords)
         feats = self._launch_groups(self._pool.view(-1), dev[: 4 * E].view(4, E), order, cp, k, offsets, c,
                                     rows[:-1], R)
         st.reset(ids)
+        if dwords:
+            return self._delta_launch(feats, dev[4 * E : 4 * E + dwords], ids, dstep, elems)
         return feats, rows
+
+    def _delta_meta(self, words, ids, k, static_rows, final):
+        """the deltas part of a tick's upload into `words` (pinned int64): the streams' step, the number of elements"""
+        n = len(ids)
+        dstep = self.dstate.step(ids, k, final=final)
+        dstep["out_rows"] = _exclusive_cumsum(dstep["rows"])
+        elems = self.dstate.fill_meta(words[: _DFIELDS * n].reshape(n, _DFIELDS), words[_DFIELDS * n :], ids, dstep,
+                                      static_rows, dstep["out_rows"][:-1], self._F)
+        return dstep, elems
+
+    def _delta_launch(self, statics, d_words, ids, dstep, elems):
+        """one pds_multistream_deltas launch over the tick's `statics`: the rows due and the next histories"""
+        torch = self._torch
+        n = len(ids)
+        rows = dstep["out_rows"]
+        out = torch.empty((int(rows[-1]), self.num_coeffs), dtype=self._tdtype, device=self.device)
+        rc = self._deltas_fn(statics.data_ptr() if statics.shape[0] else None, self._hist.data_ptr(), self.capacity,
+                             self.dstate.hist_rows, self._F, self._d_filts.data_ptr(), self._d_filt_off.data_ptr(),
+                             self._K, d_words.data_ptr(), d_words[_DFIELDS * n :].data_ptr(), n, elems,
+                             out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        _native.check(rc, "pds_multistream_deltas")
+        self.dstate.commit(ids, dstep)
+        return out, rows
 
     def _to_host(self, feats, rows, started) -> List[np.ndarray]:
         """one download into pinned memory, one synchronisation, views per stream"""

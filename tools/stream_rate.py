@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Per-tick wall time of batched streaming (multistream.StreamBatch) against a loop of single-stream compute_chunk calls.
 
-    python tools/stream_rate.py [--streams 64,1024,8192] [--ticks 200] [--loop 64,256] > profiles/<tag>_stream_rate.txt
+    python tools/stream_rate.py [--streams 64,1024,8192] [--ticks 200] [--loop 64,256] [--deltas] > profiles/<tag>_stream_rate.txt
 
 Configuration c1_readme_fbank of tests/golden/configs.json (16 kHz, 25 ms frames, 10 ms shift), 160-sample (10 ms)
 float32 chunks.  Per stream count S: `ticks` timed ticks after 20 untimed ones, each ending in a synchronisation --
 compute_chunks (host arrays in, host arrays out) and compute_chunks_packed (samples already on the GPU, features left
 there).  Real-time headroom = chunk duration / p50 tick.  The loop: compute_chunk of one chunk on each of S
-single-stream computers per tick (the host feed path, as a caller gets it).
+single-stream computers per tick (the host feed path, as a caller gets it).  --deltas: the same ticks once more
+through StreamBatch(deltas=Deltas(2)) (rows "host+d" / "packed+d": statics + delta + delta-delta, three times the
+download), and no loop.
 """
 import argparse
 import json
@@ -31,12 +33,14 @@ def main():
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--loop", default="64,256")
     ap.add_argument("--loop-ticks", type=int, default=20)
+    ap.add_argument("--deltas", action="store_true", help="also time the ticks with deltas=Deltas(2); skips the loop")
     args = ap.parse_args()
     import torch
 
     import pydrobert_speech_amd as ps
     from pydrobert_speech_amd.alias import alias_factory_subclass_from_arg
     from pydrobert_speech_amd.multistream import StreamBatch
+    from pydrobert_speech_amd.post import Deltas
 
     with open(os.path.join(ROOT, "tests", "golden", "configs.json")) as fh:
         cfg = json.load(fh)["configs"]["c1_readme_fbank"]
@@ -58,12 +62,12 @@ def main():
         ids = np.arange(S)
         d_block = torch.from_numpy(block.reshape(-1)).cuda()
         lens = np.full(S, n, dtype=np.int64)
-        for api in ("host", "packed"):
-            sb = StreamBatch(comp, capacity=S)
+        for api in ("host", "packed") + (("host+d", "packed+d") if args.deltas else ()):
+            sb = StreamBatch(comp, capacity=S, deltas=Deltas(2)) if api.endswith("+d") else StreamBatch(comp, capacity=S)
             times, frames = [], 0
             for t in range(warm + args.ticks):
                 t0 = time.perf_counter()
-                if api == "host":
+                if api.startswith("host"):
                     outs = sb.compute_chunks(ids, chunks)
                     rows = sum(len(o) for o in outs)
                 else:
@@ -78,7 +82,7 @@ def main():
             p50, p99 = pct(times, 50), pct(times, 99)
             results[f"{api}_{S}"] = dict(p50_ms=p50, p99_ms=p99, realtime_x=chunk_ms / p50, frames_per_tick=frames / args.ticks)
             print(f"{S:>8} {api:>8} {p50:>8.3f} {p99:>8.3f} {chunk_ms / p50:>12.1f} {frames / args.ticks:>11.1f}")
-    for S in [int(s) for s in args.loop.split(",")]:
+    for S in [] if args.deltas else [int(s) for s in args.loop.split(",")]:
         comps = [computer() for _ in range(S)]
         block = (3000 * rng.standard_normal((S, n))).astype(np.float32)
         times = []
