@@ -325,7 +325,9 @@ int32_t pds_feed_release(pds_feed *feed, int32_t slot);
  *   [0] stream s   [1] chunk offset in d_chunks   [2] chunk length   [3] carry length c (< frame_length)
  *   [4] drop d (first samples of the chunk skipped, frame_shift > frame_length)
  *   [5] new-carry start nc in the work span (avail - nc < frame_length, avail = c + chunk length - d)
- *   [6] work offset: the span goes to d_work[work offset .. + avail)   [7] half h the carry is read from
+ *   [6] work offset: the span goes to d_work[work offset .. + avail)
+ *   [7] bit 0: half h the carry is read from; bit 1 (pds_multistream_assemble_pcm only, ignored by the others): the
+ *       stream has been given a sample since its start or reset
  * and writes work[j] = j < c ? pool[h][s][j] : chunks[chunk offset + d + j - c] for j < avail, and
  * pool[1 - h][s][j - nc] = work[j] for nc <= j < avail.  The entries' samples are dealt in tiles of
  * pds_multistream_tile() samples: d_tile_prefix (int64[n + 1]) is the first tile of each entry (exclusive prefix sum of
@@ -339,6 +341,26 @@ int32_t pds_multistream_assemble_f32(const float *d_chunks, float *d_pool, int64
 int32_t pds_multistream_assemble_f64(const double *d_chunks, double *d_pool, int64_t capacity, int32_t frame_length,
                                      const int64_t *d_meta, const int64_t *d_tile_prefix, int32_t n,
                                      int64_t total_tiles, double *d_work, void *stream);
+/* ... for chunks of 16-bit PCM and with a pre-emphasis that runs on across ticks (StreamBatch(preemphasis=...)).
+ * work_format is the type of d_pool, d_work and d_prev, PDS_SAMPLES_F32 or PDS_SAMPLES_F64; chunk_format that of
+ * d_chunks, work_format itself or PDS_SAMPLES_I16 (converted to the working type at the load, exact; [1] counts
+ * samples of that type).  With preemph == 0 the result is that of pds_multistream_assemble_f32 / _f64 over the converted
+ * chunks and d_prev is not used.  With preemph != 0 (finite) every chunk sample that enters a work span is
+ * pre-emphasised on the way, against its predecessor in the stream's raw signal:
+ *   work[j] = (T)((double)x[ci] - preemph * (double)x[ci - 1]),  ci = d + j - c,  for c <= j < avail
+ * (float64, multiply and subtract rounded separately: pds_preemphasize_* over the stream's whole signal, bit for bit),
+ * where x[ci] = chunks[chunk offset + ci] for ci >= 0 -- a dropped sample is a predecessor like any other -- and x[-1]
+ * is the stream's previous raw sample; a stream without one ([7] bit 1 clear) keeps its sample unchanged, the
+ * reference's new[0] = old[0].  Carried samples are work values: pool[h][s][j] passes to work[j] untouched for j < c,
+ * and the new carry is written from work as above, so a finalize over the pool sees the pre-emphasised signal.  The
+ * previous raw samples live in d_prev, T[2][capacity], ping-pong with the same half as the carries: every entry of the
+ * call, with or without a work span, writes d_prev[1 - h][s] = (T) of its chunk's last sample, or d_prev[h][s] if the
+ * chunk is empty.  So with preemph != 0 a call with total_tiles == 0 still does work, and every stream's [7] bit 0
+ * must flip after every call that names it (as the carries need anyway). */
+int32_t pds_multistream_assemble_pcm(int32_t chunk_format, int32_t work_format, const void *d_chunks, void *d_pool,
+                                     int64_t capacity, int32_t frame_length, const int64_t *d_meta,
+                                     const int64_t *d_tile_prefix, int32_t n, int64_t total_tiles, void *d_work,
+                                     double preemph, void *d_prev, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * Delta features of batched streaming (StreamBatch(deltas=...)): statics + d_1 .. d_K of every stream, delayed by the

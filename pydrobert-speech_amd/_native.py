@@ -178,6 +178,9 @@ SIGNATURES = {
         c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
     "pds_multistream_assemble_f64": (
         c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
+    "pds_multistream_assemble_pcm": (
+        c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_void_p,
+                  c_double, c_void_p, c_void_p]),
     "pds_multistream_deltas_f32": (
         c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
                   c_int64, c_void_p, c_void_p]),

@@ -9,6 +9,17 @@
 // per-stream frame counts.  Work is dealt in tiles of MS_TILE samples of one stream; `tile_prefix[e]` is the first
 // tile of entry e, so one long chunk spreads over many workgroups and a tick of short ones takes one each.
 //
+// PCM chunks and pre-emphasis across ticks (StreamBatch(preemphasis=...), int16 chunks): multistream_assemble_pcm_kernel,
+// the same work with the chunk's sample type C apart from the working type T (int16 converted at the load, exact) and,
+// with PRE, every chunk sample pre-emphasised on its way into the span: x - coeff * its predecessor in the stream's raw
+// signal, pre.hip's arithmetic.  The predecessor of chunk sample ci >= 1 is chunk sample ci - 1 (dropped or not), that of
+// ci = 0 the stream's previous raw sample, kept in a second ping-pong pool T[2][capacity] -- if the stream has had a
+// sample since its start (bit MS_SEEN of the half word); without one the sample passes unchanged.  Carried samples are
+// work values and pass untouched.  An entry without a work span (a chunk dropped whole, an empty one) has no tile but
+// still hands its previous sample on: behind the tiles the grid has one lane per entry that writes the entry's new
+// previous sample (the chunk's last raw sample, or the old one under an empty chunk) to the other half.  Tiles and lanes
+// read the half the metadata names and write the other, so no block reads what another block of the launch writes.
+//
 // Delta features across ticks (StreamBatch(deltas=...)): multistream_deltas_kernel, after the STFT launches of a tick.
 // Every stream of the tick is one entry of `meta` (int64[n][MD_FIELDS]).  Its virtual sequence is its `valid` history
 // rows (pool half h) followed by its `fresh` new static rows; the entry's output rows are rows first .. first + rows of
@@ -79,6 +90,98 @@ static int32_t launch_assemble(const T *d_chunks, T *d_pool, int64_t capacity, i
   if (!d_pool || !d_meta || !d_tile_prefix || !d_work) return invalid_ms("multistream_assemble: null pointer");
   hipLaunchKernelGGL(multistream_assemble_kernel<T>, dim3((unsigned)total_tiles), dim3(MS_THREADS), 0,
                      (hipStream_t)stream, d_chunks, d_pool, capacity, frame_length, d_meta, d_tile_prefix, n, d_work);
+  PDS_HIP(hipGetLastError());
+  return PDS_OK;
+}
+
+enum { MS_SEEN = 2 };  // of the MS_HALF word (bit 0: the pool half): the stream has had a sample since its start
+
+template <typename C, typename T, bool PRE>
+__global__ __launch_bounds__(MS_THREADS) void multistream_assemble_pcm_kernel(
+    const C *__restrict__ chunks, T *__restrict__ pool, int64_t capacity, int32_t L,
+    const int64_t *__restrict__ meta, const int64_t *__restrict__ tile_prefix, int32_t n, int64_t total_tiles,
+    T *__restrict__ work, double coeff, T *__restrict__ prev) {
+  const int64_t tile = blockIdx.x;
+  if (PRE && tile >= total_tiles) {  // behind the tiles: one lane per entry, the entry's new previous sample
+    const int64_t e = (tile - total_tiles) * MS_THREADS + threadIdx.x;
+    if (e >= n) return;
+    const int64_t *m = meta + e * MS_FIELDS;
+    const int64_t s = m[MS_STREAM], len = m[MS_CHUNK_LEN], half = m[MS_HALF] & 1;
+    prev[(1 - half) * capacity + s] = len > 0 ? (T)chunks[m[MS_CHUNK_OFF] + len - 1] : prev[half * capacity + s];
+    return;
+  }
+  // entry of this tile: the last e with tile_prefix[e] <= tile (entries without samples have no tile)
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tile_prefix[mid] <= tile) lo = mid; else hi = mid;
+  }
+  const int64_t *m = meta + (int64_t)lo * MS_FIELDS;
+  const int64_t s = m[MS_STREAM], carry_len = m[MS_CARRY_LEN], new_carry = m[MS_NEW_CARRY];
+  const int64_t avail = carry_len + m[MS_CHUNK_LEN] - m[MS_DROP];
+  const int64_t chunk_at = m[MS_CHUNK_OFF] + m[MS_DROP] - carry_len;  // chunks[chunk_at + j] is work sample j >= carry_len
+  const int64_t first = m[MS_DROP] > 0 ? -1 : carry_len;  // the work sample whose predecessor is not in the chunk
+  const int64_t half = m[MS_HALF] & 1;
+  const bool seen = (m[MS_HALF] & MS_SEEN) != 0;
+  const T *carry_in = pool + (half * capacity + s) * (int64_t)L;
+  T *carry_out = pool + ((1 - half) * capacity + s) * (int64_t)L;
+  T *dst = work + m[MS_WORK_OFF];
+  const int64_t j0 = (tile - tile_prefix[lo]) * MS_TILE;
+  const int64_t j1 = j0 + MS_TILE < avail ? j0 + MS_TILE : avail;
+  // loads of the tile first, then the stores (four independent loads in flight per lane, and with PRE their four
+  // predecessors: the cache lines of the neighbouring lane's own load).  Chunk samples stay in their own type until
+  // every load is issued: a conversion beside the load would wait for it
+  const T before = PRE ? prev[half * capacity + s] : T(0);  // the stream's previous raw sample (if it has one)
+  T v[MS_PER_THREAD];
+  typename std::conditional<sizeof(C) < 4, int32_t, C>::type x[MS_PER_THREAD], p[MS_PER_THREAD];  // (whole registers)
+#pragma unroll
+  for (int q = 0; q < MS_PER_THREAD; ++q) {
+    const int64_t j = j0 + q * MS_THREADS + threadIdx.x;
+    v[q] = j < j1 && j < carry_len ? carry_in[j] : T(0);
+    x[q] = j < j1 && j >= carry_len ? chunks[chunk_at + j] : C(0);
+    if (PRE) p[q] = j < j1 && j >= carry_len && j != first ? chunks[chunk_at + j - 1] : C(0);
+  }
+#pragma unroll
+  for (int q = 0; q < MS_PER_THREAD; ++q) {  // (the conversions stay behind the loads)
+    asm volatile("" : "+v"(x[q]));
+    if (PRE) asm volatile("" : "+v"(p[q]));
+  }
+#pragma unroll
+  for (int q = 0; q < MS_PER_THREAD; ++q) {
+    const int64_t j = j0 + q * MS_THREADS + threadIdx.x;
+    if (j < j1) {
+      if (j >= carry_len) {
+        v[q] = (T)x[q];
+        // pre.hip::preemph_kernel's arithmetic (float64, multiply and subtract rounded separately); a stream's first
+        // sample has no predecessor and passes unchanged
+        if (PRE && (j != first || seen))
+          v[q] = (T)__dsub_rn((double)v[q], __dmul_rn(coeff, (double)(j != first ? (T)p[q] : before)));
+      }
+      dst[j] = v[q];
+      if (j >= new_carry && j - new_carry < L) carry_out[j - new_carry] = v[q];
+    }
+  }
+}
+
+template <typename C, typename T>
+static int32_t launch_assemble_pcm(const void *d_chunks, void *d_pool, int64_t capacity, int32_t frame_length,
+                                   const int64_t *d_meta, const int64_t *d_tile_prefix, int32_t n, int64_t total_tiles,
+                                   void *d_work, double preemph, void *d_prev, void *stream) {
+  const bool pre = preemph != 0.0;
+  // (with a pre-emphasis every entry takes part, whether it has a tile or not)
+  const int64_t blocks = total_tiles + (pre ? ((int64_t)n + MS_THREADS - 1) / MS_THREADS : 0);
+  if (n == 0 || blocks == 0) return PDS_OK;
+  if (blocks > 0x7fffffff) return invalid_ms("multistream_assemble_pcm: too many tiles in one call");
+  if (!d_pool || !d_meta || !d_tile_prefix || !d_work || (pre && !d_prev))
+    return invalid_ms("multistream_assemble_pcm: null pointer");
+  if (pre)
+    hipLaunchKernelGGL((multistream_assemble_pcm_kernel<C, T, true>), dim3((unsigned)blocks), dim3(MS_THREADS), 0,
+                       (hipStream_t)stream, (const C *)d_chunks, (T *)d_pool, capacity, frame_length, d_meta,
+                       d_tile_prefix, n, total_tiles, (T *)d_work, preemph, (T *)d_prev);
+  else
+    hipLaunchKernelGGL((multistream_assemble_pcm_kernel<C, T, false>), dim3((unsigned)blocks), dim3(MS_THREADS), 0,
+                       (hipStream_t)stream, (const C *)d_chunks, (T *)d_pool, capacity, frame_length, d_meta,
+                       d_tile_prefix, n, total_tiles, (T *)d_work, preemph, (T *)d_prev);
   PDS_HIP(hipGetLastError());
   return PDS_OK;
 }
@@ -171,6 +274,26 @@ int32_t pds_multistream_assemble_f64(const double *d_chunks, double *d_pool, int
                                      int64_t total_tiles, double *d_work, void *stream) {
   return pds::launch_assemble<double>(d_chunks, d_pool, capacity, frame_length, d_meta, d_tile_prefix, n, total_tiles,
                                       d_work, stream);
+}
+
+int32_t pds_multistream_assemble_pcm(int32_t chunk_format, int32_t work_format, const void *d_chunks, void *d_pool,
+                                     int64_t capacity, int32_t frame_length, const int64_t *d_meta,
+                                     const int64_t *d_tile_prefix, int32_t n, int64_t total_tiles, void *d_work,
+                                     double preemph, void *d_prev, void *stream) {
+  if (work_format != PDS_SAMPLES_F32 && work_format != PDS_SAMPLES_F64)
+    return pds::invalid_ms("multistream_assemble_pcm: work_format must be PDS_SAMPLES_F32 or PDS_SAMPLES_F64");
+  if (chunk_format != work_format && chunk_format != PDS_SAMPLES_I16)
+    return pds::invalid_ms("multistream_assemble_pcm: chunk_format must be work_format or PDS_SAMPLES_I16");
+  if (n < 0 || total_tiles < 0 || capacity < 0 || frame_length <= 0)
+    return pds::invalid_ms("multistream_assemble_pcm: bad size");
+  if (!(preemph == preemph) || preemph - preemph != 0.0)
+    return pds::invalid_ms("multistream_assemble_pcm: preemph must be finite");
+  const bool f64 = work_format == PDS_SAMPLES_F64;
+  auto fn = chunk_format == PDS_SAMPLES_I16
+                ? (f64 ? pds::launch_assemble_pcm<int16_t, double> : pds::launch_assemble_pcm<int16_t, float>)
+                : (f64 ? pds::launch_assemble_pcm<double, double> : pds::launch_assemble_pcm<float, float>);
+  return fn(d_chunks, d_pool, capacity, frame_length, d_meta, d_tile_prefix, n, total_tiles, d_work, preemph, d_prev,
+            stream);
 }
 
 int32_t pds_multistream_deltas_f32(const float *d_statics, float *d_hist, int64_t capacity, int32_t hist_rows,

@@ -11,11 +11,13 @@ samples of up to `capacity` streams in a device pool and takes every stream that
     sb.close()
 
     sb = StreamBatch(computer, capacity=4096, deltas=Deltas(2))   # statics + delta + delta-delta, see below
+    sb = StreamBatch(computer, capacity=4096, preemphasis=0.97)   # Preemphasize(0.97) over every stream's whole signal
 
 Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
 the same chunks: the same row counts, dtype and -- for float32 and float64 samples -- the same values bit for bit as
 the computer's plain path (``config.HOST_FEED = False``).  Which streams a tick names, and in which order, changes no
-stream's result.
+stream's result.  Chunks of 16-bit PCM (int16) give the values of the same chunks converted to `dtype` first; a tick
+whose chunks are all int16 sends them to the GPU as they are, two bytes per sample, and converts them there.
 
 A tick: the per-stream integer state (:class:`StreamState`: carry length, carry pad, pending skip, first-frame and
 started flags) is advanced on the host with numpy, which fixes every output size without reading the device; samples
@@ -35,6 +37,13 @@ writes the rows due and the next history.  ``2 H`` rows suffice: after a tick th
 H frames, the first of them reaches H further back, and while a stream has seen at most ``2 H`` frames its frame 0 is
 still in the history, so the left edge replication never needs a row that is gone.
 
+With `preemphasis` (a coefficient or a :class:`pre.Preemphasize`) a stream's rows are those of the same calls over
+``Preemphasize(coeff).apply(x)`` of its whole raw signal x, cut where the chunks were cut, bit for bit: the assemble
+launch pre-emphasises every chunk sample as it enters the work buffer, against the sample before it in the chunk or,
+for a chunk's first sample, the stream's last raw sample, which a third ping-pong pool of one sample per stream keeps
+across ticks (:attr:`StreamState.has_sample` says whether there is one).  A stream's first sample after its start or
+``finalize`` passes unchanged.  The carries hold pre-emphasised samples, so ``finalize`` needs nothing more.
+
 Not thread-safe; works on the current torch stream of the device that was current at construction.
 """
 from typing import List, Optional, Sequence, Tuple
@@ -45,12 +54,16 @@ from . import _native, config
 from .alias import alias_factory_subclass_from_arg
 from .compute import PackedLayout, ShortTimeFourierTransformFrameComputer
 from .post import Deltas, PostProcessor
+from .pre import Preemphasize, PreProcessor
 
-__all__ = ["DeltaState", "StreamBatch", "StreamState", "streaming_deltas"]
+__all__ = ["DeltaState", "StreamBatch", "StreamState", "streaming_deltas", "streaming_preemphasis"]
 
 _FIELDS = 8  # int64 per entry of pds_multistream_assemble's metadata (include/pds_amd.h)
 _DFIELDS = 8  # ... and of pds_multistream_deltas'
 _FLAG_FINAL = 2  # (bit 0 of the flags word is the pool half)
+_HAS_SAMPLE = 2  # of word 7 of the assemble metadata, beside the pool half in bit 0: the stream has a previous sample
+_SAMPLES_F32, _SAMPLES_F64, _SAMPLES_I16 = 0, 1, 2  # PDS_SAMPLES_* (include/pds_amd.h)
+_I16 = np.dtype(np.int16)
 
 
 def _exclusive_cumsum(x: np.ndarray) -> np.ndarray:
@@ -65,7 +78,11 @@ class StreamState:
 
     Per stream: ``carry_len`` samples carried (always < `frame_length`), ``carry_pad`` left reflection the carry's
     first frame still needs, ``skip`` samples still to drop (`frame_shift` > `frame_length`), ``first`` no frame
-    emitted yet, ``started`` between the first chunk and ``finalize``, ``half`` the pool half holding the carry.
+    emitted yet, ``started`` between the first chunk and ``finalize``, ``has_sample`` given at least one sample since
+    its start or last reset (a pre-emphasis has a previous sample to use), ``half`` the pool half holding the carry --
+    and the stream's previous sample, whose pool every tick that names the stream writes too.  The last two are kept
+    as the assemble metadata takes them, in one ``word`` per stream (bit 0 the half, bit 1 the flag), so a tick gathers
+    and scatters them once.
     """
 
     def __init__(self, capacity: int, frame_length: int, frame_shift: int, pad_left: int):
@@ -79,7 +96,15 @@ class StreamState:
         self.skip = np.zeros(capacity, dtype=np.int64)
         self.first = np.ones(capacity, dtype=bool)
         self.started = np.zeros(capacity, dtype=bool)
-        self.half = np.zeros(capacity, dtype=np.int64)
+        self.word = np.zeros(capacity, dtype=np.int64)
+
+    @property
+    def half(self) -> np.ndarray:
+        return self.word & 1
+
+    @property
+    def has_sample(self) -> np.ndarray:
+        return (self.word & _HAS_SAMPLE) != 0
 
     def check_ids(self, ids) -> np.ndarray:
         """`ids` as int64, or ``ValueError`` if any is unknown, negative or repeated"""
@@ -107,7 +132,7 @@ class StreamState:
         skip = self.skip[ids]
         drop = np.minimum(skip, lengths)
         skip = skip - drop
-        c, cp = self.carry_len[ids], self.carry_pad[ids]
+        c, cp, word = self.carry_len[ids], self.carry_pad[ids], self.word[ids]
         avail = c + lengths - drop
         k = np.maximum(0, (avail + cp - L) // S + 1)
         nxt = k * S - cp  # start of the next frame inside the span
@@ -120,6 +145,7 @@ class StreamState:
             next_cp=np.where(fwd, 0, np.where(emit, -nxt, cp)),
             next_first=self.first[ids] & ~emit,
             next_carry_len=avail - new_carry,
+            word=word, next_word=(word ^ 1) | (lengths > 0) * _HAS_SAMPLE,
         )
         assert (step["next_carry_len"] < L).all()
         return step
@@ -130,7 +156,8 @@ class StreamState:
         self.first[ids] = step["next_first"]
         self.carry_len[ids] = step["next_carry_len"]
         self.started[ids] = True
-        self.half[ids] ^= 1  # (the assemble kernel wrote the new carries to the other half)
+        # (the assemble kernel wrote the new carries and previous samples to the other half)
+        self.word[ids] = step["next_word"]
 
     def finalize_step(self, ids: np.ndarray) -> dict:
         """What ``finalize`` does (compute.py ``finalize``): frames `k` from the carry (`carry_len`, left pad `cp`)"""
@@ -139,7 +166,7 @@ class StreamState:
         # (a stream that has not emitted a frame still has carry_pad == pad_left)
         num = np.where(self.first[ids], (c + S // 2) // S, (c + cp + S // 2 - self.pad_left) // S)
         k = np.where((num >= 1) & (c > 0), num, 0).astype(np.int64)
-        return dict(carry_len=c, cp=cp, k=k, half=self.half[ids])
+        return dict(carry_len=c, cp=cp, k=k, half=self.word[ids] & 1)
 
     def reset(self, ids: np.ndarray) -> None:
         self.carry_len[ids] = 0
@@ -147,6 +174,32 @@ class StreamState:
         self.skip[ids] = 0
         self.first[ids] = True
         self.started[ids] = False
+        self.word[ids] &= 1
+
+
+def streaming_preemphasis(preemphasis) -> float:
+    """`preemphasis` as :class:`StreamBatch` takes it -- a coefficient, a :class:`pre.Preemphasize` or what
+    ``alias_factory_subclass_from_arg(PreProcessor, ...)`` makes one -> the coefficient, 0.0 for none (``None`` or a
+    coefficient of 0); ``ValueError`` for anything else"""
+    if preemphasis is None:
+        return 0.0
+    if isinstance(preemphasis, (bool, np.bool_)):
+        raise ValueError("StreamBatch: preemphasis must be a coefficient or a pre.Preemphasize")
+    if not isinstance(preemphasis, (int, float, np.integer, np.floating)):
+        try:
+            pre = alias_factory_subclass_from_arg(PreProcessor, preemphasis)
+        except (KeyError, TypeError, ValueError) as e:
+            raise ValueError(f"StreamBatch: preemphasis is no coefficient and no pre-processor ({e!r})") from None
+        if not isinstance(pre, Preemphasize):
+            raise ValueError("StreamBatch: preemphasis must be a coefficient or a pre.Preemphasize")
+        preemphasis = pre.coeff
+        if isinstance(preemphasis, (bool, np.bool_)) or not isinstance(
+                preemphasis, (int, float, np.integer, np.floating)):
+            raise ValueError("StreamBatch: the pre-emphasis coefficient must be a number")
+    coeff = float(preemphasis)
+    if not np.isfinite(coeff):
+        raise ValueError("StreamBatch: the pre-emphasis coefficient must be finite")
+    return coeff
 
 
 def streaming_deltas(deltas) -> Optional[Tuple[Deltas, int, int]]:
@@ -255,8 +308,15 @@ class StreamBatch:
 
     `computer`: a :class:`ShortTimeFourierTransformFrameComputer` (its plan and configuration are used; its own
     streaming state is not touched).  `capacity`: number of streams, ids ``0 .. capacity - 1``.  `dtype`: sample type,
-    float32 or float64, fixed here; chunks of another dtype are converted with numpy's rules and the features have this
-    dtype.  Device memory: the carry pool, ``2 * capacity * frame_length`` samples.
+    float32 or float64, fixed here: the working and feature type.  Chunks of another dtype are converted with numpy's
+    rules (int16 chunks on the GPU when a tick has no others).  Device memory: the carry pool,
+    ``2 * capacity * frame_length`` samples.
+
+    `preemphasis`: a coefficient, a :class:`pre.Preemphasize` (or what
+    ``alias_factory_subclass_from_arg(PreProcessor, ...)`` makes one); ``None`` or ``0``: none.  Every stream's raw
+    signal is pre-emphasised as ``Preemphasize.apply`` does it over the whole signal (float64 arithmetic, rounded to
+    `dtype`; the first sample after a start or ``finalize`` unchanged), whatever the cuts.  Additional device memory:
+    the previous-sample pool, ``2 * capacity`` elements of `dtype`.
 
     `deltas`: a :class:`post.Deltas` (or what ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one) with
     ``pad_mode="edge"``, ``concatenate=True`` and the coefficient axis as target; ``None`` or ``num_deltas == 0``: no
@@ -267,17 +327,19 @@ class StreamBatch:
     the last ``n - e``.  Additional device memory: the history pool, exactly ``2 * capacity * 2 * H * F`` elements of
     `dtype` (two halves of ``2 H`` static rows per stream), and per tick the ``(new rows, F)`` statics.
 
-    Under ``config.FLOAT64_ARITHMETIC == "float32"`` float64 samples are rounded to float32 once in the work buffer and
-    the float32 features widened (within the float32 tolerance of the computer's path, not bit for bit).
+    Under ``config.FLOAT64_ARITHMETIC == "float32"`` float64 samples are rounded to float32 once in the work buffer
+    (after a pre-emphasis, which works in float64) and the float32 features widened (within the float32 tolerance of
+    the computer's path, not bit for bit).
     """
 
-    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None):
+    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None):
         if not isinstance(computer, ShortTimeFourierTransformFrameComputer):
             raise TypeError("StreamBatch serves STFT frame computers (streaming short integration is not supported)")
         dtype = np.dtype(dtype)
         if dtype not in (np.float32, np.float64):
             raise TypeError("StreamBatch: samples must be float32 or float64")
         spec = streaming_deltas(deltas)
+        coeff = streaming_preemphasis(preemphasis)
         torch = _native.require_device()
         self._torch = torch
         self._lib = _native.lib()
@@ -295,6 +357,10 @@ class StreamBatch:
         self._tile = int(self._lib.pds_multistream_tile())
         L = computer.frame_length
         self._pool = torch.zeros((2, self.capacity, L), dtype=self._tdtype, device=self.device)
+        # every stream's previous raw sample, read from / written to the halves the carries are (none: no pool)
+        self.preemphasis = coeff
+        self._prev = torch.zeros((2, self.capacity), dtype=self._tdtype, device=self.device) if coeff else None
+        self._format = _SAMPLES_F32 if dtype == np.float32 else _SAMPLES_F64
         # pinned upload buffers (int64 words: samples, then metadata), used in turn; the event of a buffer's last
         # copy is waited for before it is written again
         self._up = [None, None]
@@ -340,8 +406,9 @@ class StreamBatch:
 
     def compute_chunks_packed(self, ids, d_samples, lengths) -> Tuple[object, np.ndarray]:
         """``compute_chunk`` of chunks already on the GPU: `d_samples` holds them back to back (1-D contiguous tensor of
-        this object's dtype on its device), ``lengths[i]`` samples for stream ``ids[i]``.  Returns ``(feats, rows)``:
-        the ``(R, num_coeffs)`` GPU tensor and the host int64 ``len(ids) + 1`` row offsets of the streams in it"""
+        this object's dtype, or of int16, on its device), ``lengths[i]`` samples for stream ``ids[i]``.  Returns
+        ``(feats, rows)``: the ``(R, num_coeffs)`` GPU tensor and the host int64 ``len(ids) + 1`` row offsets of the
+        streams in it"""
         self._check_open()
         torch = self._torch
         ids = self.state.check_ids(ids)
@@ -351,11 +418,11 @@ class StreamBatch:
         if len(lengths) and lengths.min() < 0:
             raise ValueError("negative chunk length")
         if (not isinstance(d_samples, torch.Tensor) or d_samples.device != self.device or d_samples.dim() != 1
-                or not d_samples.is_contiguous() or d_samples.dtype != self._tdtype):
-            raise ValueError(f"d_samples must be a contiguous 1-D {self.dtype} tensor on {self.device}")
+                or not d_samples.is_contiguous() or d_samples.dtype not in (self._tdtype, torch.int16)):
+            raise ValueError(f"d_samples must be a contiguous 1-D {self.dtype} or int16 tensor on {self.device}")
         if int(lengths.sum()) > d_samples.numel():
             raise ValueError("the chunks lie outside d_samples")
-        return self._chunks_tick(ids, lengths, d_samples=d_samples)
+        return self._chunks_tick(ids, lengths, d_samples=d_samples, i16=d_samples.dtype == torch.int16)
 
     def finalize(self, ids) -> List[np.ndarray]:
         """``finalize`` of streams `ids`: their last frames; the streams are reset and may be used again.  A stream
@@ -373,7 +440,7 @@ class StreamBatch:
 
     def close(self) -> None:
         """Release the pool and the pinned buffers; the object cannot be used afterwards"""
-        self._pool = self._hist = None
+        self._pool = self._hist = self._prev = None
         self._up = [None, None]
         self._up_events = [None, None]
         self._down = None
@@ -435,7 +502,7 @@ class StreamBatch:
                 self._comp.launch(signal, layout, out=feats, pad_left=int(pads[lo]))
         return feats.to(self._tdtype) if f32_arith else feats
 
-    def _chunks_tick(self, ids, lengths, host_chunks=None, d_samples=None):
+    def _chunks_tick(self, ids, lengths, host_chunks=None, d_samples=None, i16=False):
         torch = self._torch
         st = self.state
         step = st.chunk_step(ids, lengths)
@@ -452,14 +519,30 @@ class StreamBatch:
         # deltas [deltas metadata n x 8][element prefix n + 1] behind them
         total = int(lengths.sum())
         ns = (total * self.dtype.itemsize + 7) // 8 if host_chunks is not None else 0
-        words = ns + _FIELDS * n + (n + 1) + 4 * E
+        rest = _FIELDS * n + (n + 1) + 4 * E
         dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
-        slot, buf = self._staging(words + dwords)
+        slot, buf = self._staging(ns + rest + dwords)
         host = buf.numpy()
+        if ns:
+            # 16-bit PCM travels as it is, two bytes per sample, when the tick's non-empty chunks are all int16; else
+            # the chunks are converted on their way into the buffer.  numpy checks the dtypes as it copies (no loop here)
+            first = host_chunks[0] if len(host_chunks[0]) else host_chunks[int(np.argmax(lengths > 0))]
+            if first.dtype == _I16:
+                ns = (total * 2 + 7) // 8
+                try:
+                    np.concatenate(host_chunks, out=host[:ns].view(_I16)[:total], casting="no")
+                    i16 = True
+                except TypeError:  # another dtype: of empty chunks only?
+                    i16 = all(a.dtype == _I16 for a in host_chunks if len(a))
+                    if i16:
+                        np.concatenate(host_chunks, out=host[:ns].view(_I16)[:total], casting="unsafe")
+                    else:
+                        ns = (total * self.dtype.itemsize + 7) // 8
+            if not i16:
+                np.concatenate(host_chunks, out=host[:ns].view(self.dtype)[:total], casting="unsafe")
+        words = ns + rest
         if dwords:
             dstep, elems = self._delta_meta(host[words : words + dwords], ids, k, rows[:-1], final=False)
-        if ns and total:
-            np.concatenate(host_chunks, out=host[:ns].view(self.dtype)[:total], casting="unsafe")
         am = host[ns : ns + _FIELDS * n].reshape(n, _FIELDS)
         am[:, 0] = ids
         am[:, 1] = _exclusive_cumsum(lengths)[:-1]
@@ -468,18 +551,25 @@ class StreamBatch:
         am[:, 4] = step["drop"]
         am[:, 5] = step["new_carry"]
         am[:, 6] = work_off[:-1]
-        am[:, 7] = st.half[ids]
+        am[:, 7] = step["word"]
         at = ns + _FIELDS * n
         host[at : at + n + 1] = tile_prefix
         lm = host[at + n + 1 : words].reshape(4, E)
         lm[0], lm[1], lm[2], lm[3] = work_off[:-1][order], avail[order], k[order], rows[:-1][order]
         dev = self._send(slot, words + dwords)
-        samples = dev[:ns].view(self._tdtype) if host_chunks is not None else d_samples
+        samples = dev[:ns] if host_chunks is not None else d_samples  # (only its address is used)
         work = torch.empty(max(int(work_off[-1]), 1), dtype=self._tdtype, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._assemble(samples.data_ptr() if total else None, self._pool.data_ptr(), self.capacity,
-                            st.L, dev[ns:].data_ptr(), dev[at:].data_ptr(), n, int(tile_prefix[-1]),
-                            work.data_ptr(), stream)
+        if i16 or self._prev is not None:
+            rc = self._lib.pds_multistream_assemble_pcm(
+                _SAMPLES_I16 if i16 else self._format, self._format, samples.data_ptr() if total else None,
+                self._pool.data_ptr(), self.capacity, st.L, dev[ns:].data_ptr(), dev[at:].data_ptr(), n,
+                int(tile_prefix[-1]), work.data_ptr(), self.preemphasis,
+                self._prev.data_ptr() if self._prev is not None else None, stream)
+        else:
+            rc = self._assemble(samples.data_ptr() if total else None, self._pool.data_ptr(), self.capacity,
+                                st.L, dev[ns:].data_ptr(), dev[at:].data_ptr(), n, int(tile_prefix[-1]),
+                                work.data_ptr(), stream)
         _native.check(rc, "pds_multistream_assemble")
         feats = self._launch_groups(work, dev[at + n + 1 : words].view(4, E), order, cp, k, work_off[:-1], avail,
                                     rows[:-1], R)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-tick wall time of batched streaming (multistream.StreamBatch) against a loop of single-stream compute_chunk calls.
 
-    python tools/stream_rate.py [--streams 64,1024,8192] [--ticks 200] [--loop 64,256] [--deltas] > profiles/<tag>_stream_rate.txt
+    python tools/stream_rate.py [--streams 64,1024,8192] [--ticks 200] [--loop 64,256] [--deltas]
+                                [--samples {f32,i16}] [--preemph C] > profiles/<tag>_stream_rate.txt
 
 Configuration c1_readme_fbank of tests/golden/configs.json (16 kHz, 25 ms frames, 10 ms shift), 160-sample (10 ms)
 float32 chunks.  Per stream count S: `ticks` timed ticks after 20 untimed ones, each ending in a synchronisation --
@@ -9,7 +10,9 @@ compute_chunks (host arrays in, host arrays out) and compute_chunks_packed (samp
 there).  Real-time headroom = chunk duration / p50 tick.  The loop: compute_chunk of one chunk on each of S
 single-stream computers per tick (the host feed path, as a caller gets it).  --deltas: the same ticks once more
 through StreamBatch(deltas=Deltas(2)) (rows "host+d" / "packed+d": statics + delta + delta-delta, three times the
-download), and no loop.
+download), and no loop.  --samples i16: the chunks are 16-bit PCM, int16 arrays on the host (two bytes per sample over
+the link) and an int16 tensor on the GPU; --preemph C: StreamBatch(preemphasis=C), the pre-emphasis carried across
+ticks in the assemble launch.  Either leaves the loop out (a single-stream compute_chunk has no counterpart to them).
 """
 import argparse
 import json
@@ -34,6 +37,8 @@ def main():
     ap.add_argument("--loop", default="64,256")
     ap.add_argument("--loop-ticks", type=int, default=20)
     ap.add_argument("--deltas", action="store_true", help="also time the ticks with deltas=Deltas(2); skips the loop")
+    ap.add_argument("--samples", choices=("f32", "i16"), default="f32", help="sample type of the chunks")
+    ap.add_argument("--preemph", type=float, default=0.0, metavar="C", help="pre-emphasis coefficient (0: none)")
     args = ap.parse_args()
     import torch
 
@@ -53,17 +58,25 @@ def main():
     rng = np.random.default_rng(0)
     results = {"config": "c1_readme_fbank", "chunk_samples": n, "device": torch.cuda.get_device_name(0)}
     warm = 20
-    print(f"# {results['device']}, c1_readme_fbank, {n}-sample chunks ({chunk_ms:.0f} ms), {args.ticks} ticks")
+    variant = ""
+    extra = {}
+    if args.samples != "f32" or args.preemph:
+        results.update(samples=args.samples, preemph=args.preemph)
+        variant = f", {args.samples} samples" + (f", preemphasis {args.preemph:g}" if args.preemph else "")
+        extra = dict(preemphasis=args.preemph)
+    print(f"# {results['device']}, c1_readme_fbank, {n}-sample chunks ({chunk_ms:.0f} ms), {args.ticks} ticks{variant}")
     print(f"{'streams':>8} {'api':>8} {'p50 ms':>8} {'p99 ms':>8} {'x real time':>12} {'frames/tick':>11}")
     for S in [int(s) for s in args.streams.split(",")]:
         comp = computer()
         block = (3000 * rng.standard_normal((S, n))).astype(np.float32)
+        if args.samples == "i16":
+            block = np.rint(block).astype(np.int16)
         chunks = list(block)
         ids = np.arange(S)
         d_block = torch.from_numpy(block.reshape(-1)).cuda()
         lens = np.full(S, n, dtype=np.int64)
         for api in ("host", "packed") + (("host+d", "packed+d") if args.deltas else ()):
-            sb = StreamBatch(comp, capacity=S, deltas=Deltas(2)) if api.endswith("+d") else StreamBatch(comp, capacity=S)
+            sb = StreamBatch(comp, capacity=S, **(dict(deltas=Deltas(2)) if api.endswith("+d") else {}), **extra)
             times, frames = [], 0
             for t in range(warm + args.ticks):
                 t0 = time.perf_counter()
@@ -82,7 +95,7 @@ def main():
             p50, p99 = pct(times, 50), pct(times, 99)
             results[f"{api}_{S}"] = dict(p50_ms=p50, p99_ms=p99, realtime_x=chunk_ms / p50, frames_per_tick=frames / args.ticks)
             print(f"{S:>8} {api:>8} {p50:>8.3f} {p99:>8.3f} {chunk_ms / p50:>12.1f} {frames / args.ticks:>11.1f}")
-    for S in [] if args.deltas else [int(s) for s in args.loop.split(",")]:
+    for S in [] if args.deltas or variant else [int(s) for s in args.loop.split(",")]:
         comps = [computer() for _ in range(S)]
         block = (3000 * rng.standard_normal((S, n))).astype(np.float32)
         times = []
