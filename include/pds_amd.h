@@ -537,6 +537,22 @@ int32_t pds_si_batch_f64(const pds_si_plan *plan, const double *d_signal, const 
                          const int64_t *d_lengths, const int64_t *d_nframes,
                          const int64_t *d_row_off, int32_t B, int64_t max_frames, int64_t start,
                          double *d_out, int64_t out_stride, void *stream);
+/* ... with one start per utterance: d_starts (device, int64[B]) replaces the scalar, d_starts[b] for
+ * utterance b, negative values allowed as for `start`.  Many streams that each continue at their own frame,
+ * over their own kept stretch of samples, then share one call (multistream_si.py::SiStreamBatch; a stream's
+ * value is skip0 - lead + done * S - tail_at, which differs between streams still inside their first
+ * max_support samples).  Every other argument, the choice between the two float32 forms and the scratch
+ * length are those of pds_si_batch_*; with all d_starts[b] equal the features are those of pds_si_batch_*
+ * with that scalar, bit for bit.  A null d_starts is PDS_ERR_INVALID. */
+int32_t pds_si_batch_starts_f32(const pds_si_plan *plan, const float *d_signal, const int64_t *d_offsets,
+                                const int64_t *d_lengths, const int64_t *d_nframes,
+                                const int64_t *d_row_off, const int64_t *d_starts, int32_t B,
+                                int64_t max_frames, float *d_scratch, float *d_out, int64_t out_stride,
+                                void *stream);
+int32_t pds_si_batch_starts_f64(const pds_si_plan *plan, const double *d_signal, const int64_t *d_offsets,
+                                const int64_t *d_lengths, const int64_t *d_nframes,
+                                const int64_t *d_row_off, const int64_t *d_starts, int32_t B,
+                                int64_t max_frames, double *d_out, int64_t out_stride, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * Multi-GPU: gather of feature rows over RCCL (xGMI inside a node).

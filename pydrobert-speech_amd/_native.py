@@ -150,6 +150,10 @@ SIGNATURES = {
     "pds_si_plan_fft_size": (c_int32, [c_void_p]),
     "pds_si_batch_f32": (c_int32, _SI_BATCH_ARGS[:9] + [c_void_p] + _SI_BATCH_ARGS[9:]),
     "pds_si_batch_f64": (c_int32, _SI_BATCH_ARGS),
+    # ... with d_starts (one start per utterance) behind d_row_off and no scalar start
+    "pds_si_batch_starts_f32": (c_int32, _SI_BATCH_ARGS[:6] + [c_void_p] + _SI_BATCH_ARGS[6:8] + [c_void_p]
+                                + _SI_BATCH_ARGS[9:]),
+    "pds_si_batch_starts_f64": (c_int32, _SI_BATCH_ARGS[:6] + [c_void_p] + _SI_BATCH_ARGS[6:8] + _SI_BATCH_ARGS[9:]),
     "pds_cmvn_scratch_len": (c_int64, [c_int64, c_int64]),
     "pds_cmvn_stats_f32": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "pds_cmvn_stats_f64": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

@@ -48,6 +48,7 @@ struct SiArgs {
   int64_t start;
   int S, M, mpad, C, JB, use_power, use_log;
   T log_floor;
+  const int64_t *starts;  // one start per utterance (pds_si_batch_starts_*), or null: `start` for all of them
 };
 
 template <typename T>
@@ -72,8 +73,9 @@ __global__ __launch_bounds__(kSiThreads) void si_conv_kernel(const SiArgs<T> p) 
   if (j0 >= Tb) return;
   const int64_t n = p.lengths[b];
   const T *x = p.sig + p.offsets[b];
+  const int64_t start = p.starts ? p.starts[b] : p.start;  // (uniform: a scalar load beside the ones above)
   // stage sig[j0 S + start - (mpad - 1) ...], zeros outside the utterance
-  const int64_t a = j0 * S + p.start - (p.mpad - 1);
+  const int64_t a = j0 * S + start - (p.mpad - 1);
   for (int e = tid; e < seglen; e += kSiThreads) {
     const int64_t idx = a + e;
     seg[e] = (idx >= 0 && idx < n) ? x[idx] : (T)0;
@@ -152,7 +154,7 @@ template <typename T>
 static int32_t launch_si(const pds_si_plan *plan, const T *d_signal, const int64_t *d_offsets,
                          const int64_t *d_lengths, const int64_t *d_nframes,
                          const int64_t *d_row_off, int32_t B, int64_t max_frames, int64_t start,
-                         T *d_out, int64_t out_stride, void *stream) {
+                         const int64_t *d_starts, T *d_out, int64_t out_stride, void *stream) {
   if (!plan) return invalid_si("si_batch: null plan");
   if (B < 0 || max_frames < 0) return invalid_si("si_batch: negative size");
   if (B == 0 || max_frames == 0) return PDS_OK;
@@ -185,6 +187,7 @@ static int32_t launch_si(const pds_si_plan *plan, const T *d_signal, const int64
     p.window = (const T *)plan->d_window_f64;
   }
   p.start = start;
+  p.starts = d_starts;
   p.S = S;
   p.M = d.max_support;
   p.mpad = plan->mpad;
@@ -199,6 +202,21 @@ static int32_t launch_si(const pds_si_plan *plan, const T *d_signal, const int64
   hipLaunchKernelGGL(kern, grid, dim3(kSiThreads), smem, (hipStream_t)stream, p);
   PDS_HIP(hipGetLastError());
   return PDS_OK;
+}
+
+// float32: the overlap-save form when the plan has it and the caller brought scratch memory, else direct filtering
+// (d_starts: one start per utterance, or null: `start` for all of them)
+static int32_t si_batch_f32(const pds_si_plan *plan, const float *d_signal, const int64_t *d_offsets,
+                            const int64_t *d_lengths, const int64_t *d_nframes, const int64_t *d_row_off,
+                            int32_t B, int64_t max_frames, int64_t start, const int64_t *d_starts,
+                            float *d_scratch, float *d_out, int64_t out_stride, void *stream) {
+  if (plan && d_scratch && plan->fft.blocks > 0 && B > 0 && B <= 65535 && max_frames > 0 && d_signal &&
+      d_offsets && d_lengths && d_nframes && d_row_off && d_out && out_stride >= plan->d.num_coeffs &&
+      check_plan_device(plan->device, "si_batch") == PDS_OK)  // (the direct form reports a mismatch)
+    return launch_si_fft(plan, d_signal, d_offsets, d_lengths, d_nframes, d_row_off, B, max_frames, start,
+                         d_starts, d_scratch, d_out, out_stride, stream);
+  return launch_si<float>(plan, d_signal, d_offsets, d_lengths, d_nframes, d_row_off, B, max_frames, start,
+                          d_starts, d_out, out_stride, stream);
 }
 
 }  // namespace pds
@@ -264,13 +282,8 @@ int32_t pds_si_batch_f32(const pds_si_plan *plan, const float *d_signal, const i
                          const int64_t *d_lengths, const int64_t *d_nframes,
                          const int64_t *d_row_off, int32_t B, int64_t max_frames, int64_t start,
                          float *d_scratch, float *d_out, int64_t out_stride, void *stream) {
-  if (plan && d_scratch && plan->fft.blocks > 0 && B > 0 && B <= 65535 && max_frames > 0 && d_signal &&
-      d_offsets && d_lengths && d_nframes && d_row_off && d_out && out_stride >= plan->d.num_coeffs &&
-      pds::check_plan_device(plan->device, "si_batch") == PDS_OK)  // (the direct form reports a mismatch)
-    return pds::launch_si_fft(plan, d_signal, d_offsets, d_lengths, d_nframes, d_row_off, B, max_frames,
-                              start, d_scratch, d_out, out_stride, stream);
-  return pds::launch_si<float>(plan, d_signal, d_offsets, d_lengths, d_nframes, d_row_off, B,
-                               max_frames, start, d_out, out_stride, stream);
+  return pds::si_batch_f32(plan, d_signal, d_offsets, d_lengths, d_nframes, d_row_off, B, max_frames, start,
+                           nullptr, d_scratch, d_out, out_stride, stream);
 }
 
 int32_t pds_si_batch_f64(const pds_si_plan *plan, const double *d_signal, const int64_t *d_offsets,
@@ -278,7 +291,26 @@ int32_t pds_si_batch_f64(const pds_si_plan *plan, const double *d_signal, const 
                          const int64_t *d_row_off, int32_t B, int64_t max_frames, int64_t start,
                          double *d_out, int64_t out_stride, void *stream) {
   return pds::launch_si<double>(plan, d_signal, d_offsets, d_lengths, d_nframes, d_row_off, B,
-                                max_frames, start, d_out, out_stride, stream);
+                                max_frames, start, nullptr, d_out, out_stride, stream);
+}
+
+int32_t pds_si_batch_starts_f32(const pds_si_plan *plan, const float *d_signal, const int64_t *d_offsets,
+                                const int64_t *d_lengths, const int64_t *d_nframes,
+                                const int64_t *d_row_off, const int64_t *d_starts, int32_t B,
+                                int64_t max_frames, float *d_scratch, float *d_out, int64_t out_stride,
+                                void *stream) {
+  if (!d_starts) return pds::invalid_si("si_batch_starts: null d_starts");
+  return pds::si_batch_f32(plan, d_signal, d_offsets, d_lengths, d_nframes, d_row_off, B, max_frames, 0,
+                           d_starts, d_scratch, d_out, out_stride, stream);
+}
+
+int32_t pds_si_batch_starts_f64(const pds_si_plan *plan, const double *d_signal, const int64_t *d_offsets,
+                                const int64_t *d_lengths, const int64_t *d_nframes,
+                                const int64_t *d_row_off, const int64_t *d_starts, int32_t B,
+                                int64_t max_frames, double *d_out, int64_t out_stride, void *stream) {
+  if (!d_starts) return pds::invalid_si("si_batch_starts: null d_starts");
+  return pds::launch_si<double>(plan, d_signal, d_offsets, d_lengths, d_nframes, d_row_off, B,
+                                max_frames, 0, d_starts, d_out, out_stride, stream);
 }
 
 }  // extern "C"

@@ -76,6 +76,7 @@ struct SiFftArgs {
   int64_t start;
   int S, C, blocks, use_power;
   int c_per_group;          // filters a workgroup walks (blockIdx.z picks the group): small batches are split over the filters too
+  const int64_t *starts;    // one start per utterance (pds_si_batch_starts_f32), or null: `start` for all of them
 };
 
 // lower half-wave: x(lane) + x(lane + 32); upper half-wave: x(lane - 32) - x(lane)  (sgn = +1 / -1)
@@ -178,7 +179,8 @@ __global__ __launch_bounds__(kWaves * 64, 1) void si_fft_kernel(const SiFftArgs 
   const float *x = p.sig + p.offsets[b];
   // element m of the stretch is signal sample d V + start - (NT - V) + m: the last V outputs of
   // the circular convolution are the filtered samples d V .. d V + V - 1
-  const int64_t s0 = d * V + p.start - (NT - V);
+  const int64_t start = p.starts ? p.starts[b] : p.start;  // (uniform: a scalar load beside the ones above)
+  const int64_t s0 = d * V + start - (NT - V);
   const int first_valid = NT - V;
   // sample held in register q (time layout) and bin held in register q (frequency layout)
   auto sample_of = [&](int q) { return BIG ? 64 * q + 2 * l + hw : kL * q + l; };
@@ -441,8 +443,8 @@ int64_t si_fft_scratch_len(const pds_si_plan *plan, int32_t B, int64_t max_frame
 
 int32_t launch_si_fft(const pds_si_plan *plan, const float *d_signal, const int64_t *d_offsets,
                       const int64_t *d_lengths, const int64_t *d_nframes, const int64_t *d_row_off,
-                      int32_t B, int64_t max_frames, int64_t start, float *d_scratch, float *d_out,
-                      int64_t out_stride, void *stream) {
+                      int32_t B, int64_t max_frames, int64_t start, const int64_t *d_starts, float *d_scratch,
+                      float *d_out, int64_t out_stride, void *stream) {
   const pds_si_desc &d = plan->d;
   const int64_t transforms = transforms_for(plan, max_frames);
   SiFftArgs p;
@@ -457,6 +459,7 @@ int32_t launch_si_fft(const pds_si_plan *plan, const float *d_signal, const int6
   p.twiddle2k = plan->fft.d_twiddle2k;
   p.window = plan->d_window_f32;
   p.start = start;
+  p.starts = d_starts;
   p.S = d.frame_shift;
   p.C = d.num_coeffs;
   p.blocks = plan->fft.blocks;

@@ -303,48 +303,27 @@ class DeltaState:
         return int(prefix[-1])
 
 
-class StreamBatch:
-    """``compute_chunk`` / ``finalize`` of many streams of one STFT computer, one tick per call
+class _TickBatch:
+    """What :class:`StreamBatch` and :class:`multistream_si.SiStreamBatch` share: the public calls, the pools, the pinned
+    staging, the assemble launch, the delta rows and the download of a tick.  A subclass sets ``state`` (its host state
+    machine: ``check_ids``, ``started``), then calls :func:`_setup`, and implements ``_chunks_tick`` and
+    ``_finalize_tick``."""
 
-    `computer`: a :class:`ShortTimeFourierTransformFrameComputer` (its plan and configuration are used; its own
-    streaming state is not touched).  `capacity`: number of streams, ids ``0 .. capacity - 1``.  `dtype`: sample type,
-    float32 or float64, fixed here: the working and feature type.  Chunks of another dtype are converted with numpy's
-    rules (int16 chunks on the GPU when a tick has no others).  Device memory: the carry pool,
-    ``2 * capacity * frame_length`` samples.
-
-    `preemphasis`: a coefficient, a :class:`pre.Preemphasize` (or what
-    ``alias_factory_subclass_from_arg(PreProcessor, ...)`` makes one); ``None`` or ``0``: none.  Every stream's raw
-    signal is pre-emphasised as ``Preemphasize.apply`` does it over the whole signal (float64 arithmetic, rounded to
-    `dtype`; the first sample after a start or ``finalize`` unchanged), whatever the cuts.  Additional device memory:
-    the previous-sample pool, ``2 * capacity`` elements of `dtype`.
-
-    `deltas`: a :class:`post.Deltas` (or what ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one) with
-    ``pad_mode="edge"``, ``concatenate=True`` and the coefficient axis as target; ``None`` or ``num_deltas == 0``: no
-    deltas.  With ``F = computer.num_coeffs``, ``K = num_deltas`` and ``H = K * context_window`` (:attr:`lookahead`)
-    every stream's rows become ``[static, d_1 .. d_K]`` (``num_coeffs == (K + 1) * F``), equal bit for bit to
-    ``deltas.apply(X, axis=0)`` of its concatenated statics X and delayed by H frames: when a stream has produced n
-    static frames and been given e rows, a ``compute_chunks`` call returns ``max(0, n - H) - e`` rows and ``finalize``
-    the last ``n - e``.  Additional device memory: the history pool, exactly ``2 * capacity * 2 * H * F`` elements of
-    `dtype` (two halves of ``2 H`` static rows per stream), and per tick the ``(new rows, F)`` statics.
-
-    Under ``config.FLOAT64_ARITHMETIC == "float32"`` float64 samples are rounded to float32 once in the work buffer
-    (after a pre-emphasis, which works in float64) and the float32 features widened (within the float32 tolerance of
-    the computer's path, not bit for bit).
-    """
-
-    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None):
-        if not isinstance(computer, ShortTimeFourierTransformFrameComputer):
-            raise TypeError("StreamBatch serves STFT frame computers (streaming short integration is not supported)")
+    @staticmethod
+    def _check_args(dtype, deltas, preemphasis):
+        """the constructor arguments both classes take -> ``(dtype, deltas spec, coefficient)``, before any device is
+        touched"""
         dtype = np.dtype(dtype)
         if dtype not in (np.float32, np.float64):
             raise TypeError("StreamBatch: samples must be float32 or float64")
-        spec = streaming_deltas(deltas)
-        coeff = streaming_preemphasis(preemphasis)
-        torch = _native.require_device()
+        return dtype, streaming_deltas(deltas), streaming_preemphasis(preemphasis)
+
+    def _setup(self, torch, computer, row_length: int, dtype, spec, coeff):
+        """the device side: `computer`'s plan, the carry pool of ``2 * capacity * row_length`` samples, the
+        previous-sample pool (with a pre-emphasis), the staging buffers and the history pool of the deltas"""
         self._torch = torch
         self._lib = _native.lib()
         self.dtype = dtype
-        self.state = StreamState(capacity, computer.frame_length, computer.frame_shift, computer.pad_left)
         self.capacity = self.state.capacity
         self.device = torch.device("cuda", torch.cuda.current_device())
         self._F = computer.num_coeffs  # statics per row
@@ -355,8 +334,8 @@ class StreamBatch:
         self._assemble = (self._lib.pds_multistream_assemble_f32 if dtype == np.float32
                           else self._lib.pds_multistream_assemble_f64)
         self._tile = int(self._lib.pds_multistream_tile())
-        L = computer.frame_length
-        self._pool = torch.zeros((2, self.capacity, L), dtype=self._tdtype, device=self.device)
+        self._row_length = int(row_length)
+        self._pool = torch.zeros((2, self.capacity, self._row_length), dtype=self._tdtype, device=self.device)
         # every stream's previous raw sample, read from / written to the halves the carries are (none: no pool)
         self.preemphasis = coeff
         self._prev = torch.zeros((2, self.capacity), dtype=self._tdtype, device=self.device) if coeff else None
@@ -455,7 +434,7 @@ class StreamBatch:
 
     def _check_open(self):
         if self._pool is None:
-            raise ValueError("StreamBatch is closed")
+            raise ValueError(f"{type(self).__name__} is closed")
 
     def _staging(self, words: int):
         """the next pinned upload buffer (int64 numpy view of at least `words`), free to write"""
@@ -481,6 +460,130 @@ class StreamBatch:
             ev = self._up_events[slot] = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
         return dev
+
+    def _pack_chunks(self, host, host_chunks, lengths, total):
+        """the samples of a tick's host chunks (`total` > 0 of them) into the front of the pinned words `host`; returns
+        the words they take and whether they went as 16-bit PCM"""
+        # 16-bit PCM travels as it is, two bytes per sample, when the tick's non-empty chunks are all int16; else
+        # the chunks are converted on their way into the buffer.  numpy checks the dtypes as it copies (no loop here)
+        i16 = False
+        ns = (total * self.dtype.itemsize + 7) // 8
+        first = host_chunks[0] if len(host_chunks[0]) else host_chunks[int(np.argmax(lengths > 0))]
+        if first.dtype == _I16:
+            ns = (total * 2 + 7) // 8
+            try:
+                np.concatenate(host_chunks, out=host[:ns].view(_I16)[:total], casting="no")
+                i16 = True
+            except TypeError:  # another dtype: of empty chunks only?
+                i16 = all(a.dtype == _I16 for a in host_chunks if len(a))
+                if i16:
+                    np.concatenate(host_chunks, out=host[:ns].view(_I16)[:total], casting="unsafe")
+                else:
+                    ns = (total * self.dtype.itemsize + 7) // 8
+        if not i16:
+            np.concatenate(host_chunks, out=host[:ns].view(self.dtype)[:total], casting="unsafe")
+        return ns, i16
+
+    def _assemble_launch(self, samples, i16, d_meta, d_tile_prefix, n, tiles, work_len):
+        """one pds_multistream_assemble launch: the tick's work buffer (returned) and the new carries, in the other
+        pool half; `samples`: the device tensor the chunks start in (only its address is used; None: no samples)"""
+        torch = self._torch
+        work = torch.empty(max(work_len, 1), dtype=self._tdtype, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        chunks = samples.data_ptr() if samples is not None else None
+        if i16 or self._prev is not None:
+            rc = self._lib.pds_multistream_assemble_pcm(
+                _SAMPLES_I16 if i16 else self._format, self._format, chunks, self._pool.data_ptr(), self.capacity,
+                self._row_length, d_meta.data_ptr(), d_tile_prefix.data_ptr(), n, tiles, work.data_ptr(),
+                self.preemphasis, self._prev.data_ptr() if self._prev is not None else None, stream)
+        else:
+            rc = self._assemble(chunks, self._pool.data_ptr(), self.capacity, self._row_length, d_meta.data_ptr(),
+                                d_tile_prefix.data_ptr(), n, tiles, work.data_ptr(), stream)
+        _native.check(rc, "pds_multistream_assemble")
+        return work
+
+    def _delta_meta(self, words, ids, k, static_rows, final):
+        """the deltas part of a tick's upload into `words` (pinned int64): the streams' step, the number of elements"""
+        n = len(ids)
+        dstep = self.dstate.step(ids, k, final=final)
+        dstep["out_rows"] = _exclusive_cumsum(dstep["rows"])
+        elems = self.dstate.fill_meta(words[: _DFIELDS * n].reshape(n, _DFIELDS), words[_DFIELDS * n :], ids, dstep,
+                                      static_rows, dstep["out_rows"][:-1], self._F)
+        return dstep, elems
+
+    def _delta_launch(self, statics, d_words, ids, dstep, elems):
+        """one pds_multistream_deltas launch over the tick's `statics`: the rows due and the next histories"""
+        torch = self._torch
+        n = len(ids)
+        rows = dstep["out_rows"]
+        out = torch.empty((int(rows[-1]), self.num_coeffs), dtype=self._tdtype, device=self.device)
+        rc = self._deltas_fn(statics.data_ptr() if statics.shape[0] else None, self._hist.data_ptr(), self.capacity,
+                             self.dstate.hist_rows, self._F, self._d_filts.data_ptr(), self._d_filt_off.data_ptr(),
+                             self._K, d_words.data_ptr(), d_words[_DFIELDS * n :].data_ptr(), n, elems,
+                             out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        _native.check(rc, "pds_multistream_deltas")
+        self.dstate.commit(ids, dstep)
+        return out, rows
+
+    def _to_host(self, feats, rows, started) -> List[np.ndarray]:
+        """one download into pinned memory, one synchronisation, views per stream"""
+        torch = self._torch
+        R, C = feats.shape
+        if R:
+            if self._down is None or self._down.numel() < R * C:
+                size = 1 << 16
+                while size < R * C:
+                    size <<= 1
+                self._down = torch.empty(size, dtype=self._tdtype, pin_memory=True)
+            pinned = self._down[: R * C].view(R, C)
+            pinned.copy_(feats, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+            host = pinned.numpy().copy()
+        else:
+            host = np.empty((0, C), dtype=self.dtype)
+        idle = np.empty((0, C), dtype=np.float64)
+        return [host[a:b] if s else idle.copy() for a, b, s in zip(rows[:-1].tolist(), rows[1:].tolist(), started)]
+
+
+class StreamBatch(_TickBatch):
+    """``compute_chunk`` / ``finalize`` of many streams of one STFT computer, one tick per call
+
+    `computer`: a :class:`ShortTimeFourierTransformFrameComputer` (its plan and configuration are used; its own
+    streaming state is not touched).  `capacity`: number of streams, ids ``0 .. capacity - 1``.  `dtype`: sample type,
+    float32 or float64, fixed here: the working and feature type.  Chunks of another dtype are converted with numpy's
+    rules (int16 chunks on the GPU when a tick has no others).  Device memory: the carry pool,
+    ``2 * capacity * frame_length`` samples.
+
+    `preemphasis`: a coefficient, a :class:`pre.Preemphasize` (or what
+    ``alias_factory_subclass_from_arg(PreProcessor, ...)`` makes one); ``None`` or ``0``: none.  Every stream's raw
+    signal is pre-emphasised as ``Preemphasize.apply`` does it over the whole signal (float64 arithmetic, rounded to
+    `dtype`; the first sample after a start or ``finalize`` unchanged), whatever the cuts.  Additional device memory:
+    the previous-sample pool, ``2 * capacity`` elements of `dtype`.
+
+    `deltas`: a :class:`post.Deltas` (or what ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one) with
+    ``pad_mode="edge"``, ``concatenate=True`` and the coefficient axis as target; ``None`` or ``num_deltas == 0``: no
+    deltas.  With ``F = computer.num_coeffs``, ``K = num_deltas`` and ``H = K * context_window`` (:attr:`lookahead`)
+    every stream's rows become ``[static, d_1 .. d_K]`` (``num_coeffs == (K + 1) * F``), equal bit for bit to
+    ``deltas.apply(X, axis=0)`` of its concatenated statics X and delayed by H frames: when a stream has produced n
+    static frames and been given e rows, a ``compute_chunks`` call returns ``max(0, n - H) - e`` rows and ``finalize``
+    the last ``n - e``.  Additional device memory: the history pool, exactly ``2 * capacity * 2 * H * F`` elements of
+    `dtype` (two halves of ``2 H`` static rows per stream), and per tick the ``(new rows, F)`` statics.
+
+    Under ``config.FLOAT64_ARITHMETIC == "float32"`` float64 samples are rounded to float32 once in the work buffer
+    (after a pre-emphasis, which works in float64) and the float32 features widened (within the float32 tolerance of
+    the computer's path, not bit for bit).
+    """
+
+    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None):
+        if not isinstance(computer, ShortTimeFourierTransformFrameComputer):
+            raise TypeError("StreamBatch serves STFT frame computers (streaming short integration is not supported "
+                            "here: multistream_si.SiStreamBatch serves those)")
+        dtype, spec, coeff = self._check_args(dtype, deltas, preemphasis)
+        torch = _native.require_device()
+        self.state = StreamState(capacity, computer.frame_length, computer.frame_shift, computer.pad_left)
+        self._setup(torch, computer, computer.frame_length, dtype, spec, coeff)
+
+    # ---- a tick ---------------------------------------------------------------------
 
     def _launch_groups(self, signal, d_lm, order, cp, k, offsets, lengths, row_off, R):
         """the STFT batch launches of one tick: streams `order` (sorted by carry pad), one launch per distinct pad;
@@ -524,22 +627,7 @@ class StreamBatch:
         slot, buf = self._staging(ns + rest + dwords)
         host = buf.numpy()
         if ns:
-            # 16-bit PCM travels as it is, two bytes per sample, when the tick's non-empty chunks are all int16; else
-            # the chunks are converted on their way into the buffer.  numpy checks the dtypes as it copies (no loop here)
-            first = host_chunks[0] if len(host_chunks[0]) else host_chunks[int(np.argmax(lengths > 0))]
-            if first.dtype == _I16:
-                ns = (total * 2 + 7) // 8
-                try:
-                    np.concatenate(host_chunks, out=host[:ns].view(_I16)[:total], casting="no")
-                    i16 = True
-                except TypeError:  # another dtype: of empty chunks only?
-                    i16 = all(a.dtype == _I16 for a in host_chunks if len(a))
-                    if i16:
-                        np.concatenate(host_chunks, out=host[:ns].view(_I16)[:total], casting="unsafe")
-                    else:
-                        ns = (total * self.dtype.itemsize + 7) // 8
-            if not i16:
-                np.concatenate(host_chunks, out=host[:ns].view(self.dtype)[:total], casting="unsafe")
+            ns, i16 = self._pack_chunks(host, host_chunks, lengths, total)
         words = ns + rest
         if dwords:
             dstep, elems = self._delta_meta(host[words : words + dwords], ids, k, rows[:-1], final=False)
@@ -558,19 +646,8 @@ class StreamBatch:
         lm[0], lm[1], lm[2], lm[3] = work_off[:-1][order], avail[order], k[order], rows[:-1][order]
         dev = self._send(slot, words + dwords)
         samples = dev[:ns] if host_chunks is not None else d_samples  # (only its address is used)
-        work = torch.empty(max(int(work_off[-1]), 1), dtype=self._tdtype, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if i16 or self._prev is not None:
-            rc = self._lib.pds_multistream_assemble_pcm(
-                _SAMPLES_I16 if i16 else self._format, self._format, samples.data_ptr() if total else None,
-                self._pool.data_ptr(), self.capacity, st.L, dev[ns:].data_ptr(), dev[at:].data_ptr(), n,
-                int(tile_prefix[-1]), work.data_ptr(), self.preemphasis,
-                self._prev.data_ptr() if self._prev is not None else None, stream)
-        else:
-            rc = self._assemble(samples.data_ptr() if total else None, self._pool.data_ptr(), self.capacity,
-                                st.L, dev[ns:].data_ptr(), dev[at:].data_ptr(), n, int(tile_prefix[-1]),
-                                work.data_ptr(), stream)
-        _native.check(rc, "pds_multistream_assemble")
+        work = self._assemble_launch(samples if total else None, i16, dev[ns:], dev[at:], n, int(tile_prefix[-1]),
+                                     int(work_off[-1]))
         feats = self._launch_groups(work, dev[at + n + 1 : words].view(4, E), order, cp, k, work_off[:-1], avail,
                                     rows[:-1], R)
         st.commit_chunks(ids, step)
@@ -602,45 +679,3 @@ class StreamBatch:
         if dwords:
             return self._delta_launch(feats, dev[4 * E : 4 * E + dwords], ids, dstep, elems)
         return feats, rows
-
-    def _delta_meta(self, words, ids, k, static_rows, final):
-        """the deltas part of a tick's upload into `words` (pinned int64): the streams' step, the number of elements"""
-        n = len(ids)
-        dstep = self.dstate.step(ids, k, final=final)
-        dstep["out_rows"] = _exclusive_cumsum(dstep["rows"])
-        elems = self.dstate.fill_meta(words[: _DFIELDS * n].reshape(n, _DFIELDS), words[_DFIELDS * n :], ids, dstep,
-                                      static_rows, dstep["out_rows"][:-1], self._F)
-        return dstep, elems
-
-    def _delta_launch(self, statics, d_words, ids, dstep, elems):
-        """one pds_multistream_deltas launch over the tick's `statics`: the rows due and the next histories"""
-        torch = self._torch
-        n = len(ids)
-        rows = dstep["out_rows"]
-        out = torch.empty((int(rows[-1]), self.num_coeffs), dtype=self._tdtype, device=self.device)
-        rc = self._deltas_fn(statics.data_ptr() if statics.shape[0] else None, self._hist.data_ptr(), self.capacity,
-                             self.dstate.hist_rows, self._F, self._d_filts.data_ptr(), self._d_filt_off.data_ptr(),
-                             self._K, d_words.data_ptr(), d_words[_DFIELDS * n :].data_ptr(), n, elems,
-                             out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-        _native.check(rc, "pds_multistream_deltas")
-        self.dstate.commit(ids, dstep)
-        return out, rows
-
-    def _to_host(self, feats, rows, started) -> List[np.ndarray]:
-        """one download into pinned memory, one synchronisation, views per stream"""
-        torch = self._torch
-        R, C = feats.shape
-        if R:
-            if self._down is None or self._down.numel() < R * C:
-                size = 1 << 16
-                while size < R * C:
-                    size <<= 1
-                self._down = torch.empty(size, dtype=self._tdtype, pin_memory=True)
-            pinned = self._down[: R * C].view(R, C)
-            pinned.copy_(feats, non_blocking=True)
-            torch.cuda.current_stream(self.device).synchronize()
-            host = pinned.numpy().copy()
-        else:
-            host = np.empty((0, C), dtype=self.dtype)
-        idle = np.empty((0, C), dtype=np.float64)
-        return [host[a:b] if s else idle.copy() for a, b, s in zip(rows[:-1].tolist(), rows[1:].tolist(), started)]

@@ -1,0 +1,297 @@
+"""Batched streaming for short-integration computers: ``compute_chunk`` / ``finalize`` of many streams per launch
+
+:class:`multistream.StreamBatch` serves the STFT computer; :class:`SiStreamBatch` is its counterpart for
+:class:`si.ShortIntegrationFrameComputer` (alias ``si``), with the same public surface:
+
+    sb = SiStreamBatch(computer, capacity=4096)       # computer: a short-integration frame computer
+    outs = sb.compute_chunks(ids, chunks)             # ids: distinct ints; chunks: 1-D arrays -> list of (k_i, C)
+    outs = sb.finalize(ids)                           # the last frames; the streams are reset and may be reused
+    feats, rows = sb.compute_chunks_packed(ids, d_samples, lengths)   # GPU in, GPU out
+    sb.close()
+
+    sb = SiStreamBatch(computer, capacity=4096, deltas=Deltas(2), preemphasis=0.97)   # as for StreamBatch
+
+Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
+the same chunks: the same row counts, dtype and -- for float32 and float64 samples alike -- the same values bit for
+bit.  That holds by construction: a stream's work span of a tick (carried samples, then the chunk) is exactly the
+private computer's kept tail after its concatenation, the kernel's `start` and the frame count are the same numbers,
+and positions outside ``[0, length)`` read as zero in both, so the direct kernel and the overlap-save transforms see
+identical inputs at identical alignment; neither's arithmetic depends on how many utterances or frames a call has.
+Which streams a tick names, and in which order, changes no stream's result.  Chunks of 16-bit PCM (int16) give the
+values of the same chunks converted to `dtype` first (the single-stream computer refuses integer chunks; the batch
+takes them as ``StreamBatch`` does).  With `deltas` a stream's rows are ``Deltas.apply`` of its whole sequence of
+statics, delayed by :attr:`SiStreamBatch.lookahead` frames; with `preemphasis` they are those of the pre-emphasised
+whole signal; both bit for bit, as documented in :mod:`multistream`.
+
+A tick: :class:`SiStreamState` -- the array form of ``si.py``'s ``compute_chunk`` / ``_emit`` / ``finalize``
+bookkeeping -- is advanced on the host, which fixes every size without reading the device; samples and metadata go up
+in one copy from pinned memory; one ``pds_multistream_assemble_*`` launch writes the tick's packed work buffer (carry
++ chunk of every stream) and the new carries into the other pool half; one ``pds_si_batch_starts_*`` call computes
+the frames of every stream that has any, each continued at its own `start` (float32: the plan's overlap-save form
+when it has one, else direct filtering; float64: direct filtering -- the choices the single-stream computer makes);
+optionally one ``pds_multistream_deltas_*`` launch; one download.  ``finalize`` reads the carries where they lie in
+the pool.
+
+The per-utterance start is what makes one call enough.  A stream's `start` is ``skip0 - lead + done * S - tail_at``:
+the position of its next frame's first integrated sample, relative to the first sample it still keeps.  Once
+``keep_from = skip0 - lead + done * S - (M - 1)`` has passed 0 the kept tail starts there and `start` is ``M - 1`` for
+every stream; before that -- the stream's first ``M - 1`` or so samples -- ``tail_at`` is 0 and `start` grows with
+``done``, so streams begun at different times differ.
+
+The carried tail is bounded: ``carry_len < max(M - 1, skip0) + 2 S`` (``M`` the longest support, ``S`` the frame shift).
+After any call ``waiting < 2 S`` (a call emits ``waiting // S - 1`` frames), and with ``P`` samples received so far
+``P = waiting + skip0 - lead + done * S`` once the skip is consumed.  While no frame has been emitted ``tail_at`` is 0
+and the tail is everything: ``P < skip0`` under a pending skip, else ``P < skip0 + 2 S`` (``lead > 0`` only with
+``skip0 == 0``).  After an emission ``tail_at = max(0, keep_from)``, so ``P - tail_at <= P - keep_from = waiting + M - 1
+< M - 1 + 2 S``.  That bound is the pool's row length, and :func:`SiStreamState.chunk_step` asserts it.
+
+Not thread-safe; works on the current torch stream of the device that was current at construction.
+"""
+from typing import Tuple
+
+import numpy as np
+
+from . import _native
+from .compute import _MAX_UTTS_PER_CALL
+from .multistream import _DFIELDS, _FIELDS, _HAS_SAMPLE, StreamState, _exclusive_cumsum, _TickBatch
+from .si import ShortIntegrationFrameComputer
+
+__all__ = ["SiStreamBatch", "SiStreamState"]
+
+
+class SiStreamState:
+    """Host bookkeeping of many short-integration streams: ``si.py``'s ``_reset_stream`` / ``compute_chunk`` / ``_emit``
+    / ``finalize`` applied to arrays of streams.  Needs no device.
+
+    Geometry (one computer's): `frame_shift` S, `max_support` M, `translation`, `skip0` samples consumed before
+    integration starts, `lead` virtual zeros in front (at most one of the two is positive), `centered` frames.
+
+    Per stream: ``done`` frames emitted, ``waiting`` integrated samples received but not yet framed, ``skip_left`` of the
+    skip still pending, ``tail_at`` stream position of the first kept sample, ``carry_len`` kept samples (always
+    < :attr:`row_length`), ``started`` between the first chunk and ``finalize``, and the pool half / has-sample ``word``
+    laid out as in :class:`multistream.StreamState`.
+    """
+
+    def __init__(self, capacity: int, frame_shift: int, max_support: int, translation: int, skip0: int, lead: int,
+                 centered: bool):
+        capacity = int(capacity)
+        if capacity <= 0:
+            raise ValueError("capacity must be positive")
+        self.capacity = capacity
+        self.S, self.M, self.translation = int(frame_shift), int(max_support), int(translation)
+        self.skip0, self.lead, self.centered = int(skip0), int(lead), bool(centered)
+        if self.S < 1 or self.M < 1 or self.skip0 < 0 or self.lead < 0 or (self.skip0 and self.lead):
+            raise ValueError("not the geometry of a short-integration computer")
+        self.frame_length = self.M + self.S - 1
+        # carry_len < row_length always (module docstring); the row length of the carry pool
+        self.row_length = max(self.M - 1, self.skip0) + 2 * self.S
+        self.done = np.zeros(capacity, dtype=np.int64)
+        self.waiting = np.zeros(capacity, dtype=np.int64)
+        self.skip_left = np.zeros(capacity, dtype=np.int64)
+        self.tail_at = np.zeros(capacity, dtype=np.int64)
+        self.carry_len = np.zeros(capacity, dtype=np.int64)
+        self.started = np.zeros(capacity, dtype=bool)
+        self.word = np.zeros(capacity, dtype=np.int64)
+
+    @classmethod
+    def of(cls, computer: ShortIntegrationFrameComputer, capacity: int) -> "SiStreamState":
+        """the state of `capacity` streams of `computer`"""
+        return cls(capacity, computer.frame_shift, computer._max_support, computer._translation, computer._skip0,
+                   computer._lead, computer.frame_style == "centered")
+
+    half = StreamState.half
+    has_sample = StreamState.has_sample
+    check_ids = StreamState.check_ids
+
+    def _start(self, done, tail_at):
+        """the kernel's `start` for a span that begins at stream position `tail_at`, continued at frame `done`"""
+        return self.skip0 - self.lead + done * self.S - tail_at
+
+    def chunk_step(self, ids: np.ndarray, lengths: np.ndarray) -> dict:
+        """What ``compute_chunk`` of chunks of `lengths` does to streams `ids`, without changing the state: per stream
+        the carry (`carry_len`), the work span `avail` = carry + chunk (nothing of a chunk is dropped: skipped samples
+        stay in the tail until ``keep_from`` passes them), its frame count `k`, the kernel's `start` for the span, where
+        the new carry starts in the span (`new_carry`: ``keep_from - tail_at``, 0 when no frame is emitted) and the new
+        state (``commit_chunks`` applies it)"""
+        S = self.S
+        lengths = np.asarray(lengths, dtype=np.int64)
+        fresh = ~self.started[ids]  # the first chunk since the start or a finalize
+        skip_left = np.where(fresh, self.skip0, self.skip_left[ids])
+        waiting = np.where(fresh, self.lead, self.waiting[ids])
+        done, tail_at, c, word = self.done[ids], self.tail_at[ids], self.carry_len[ids], self.word[ids]
+        consumed = np.minimum(skip_left, lengths)
+        skip_left = skip_left - consumed
+        waiting = waiting + lengths - consumed
+        avail = c + lengths
+        k = np.maximum(0, waiting // S - 1)
+        next_done = done + k
+        # samples before the first one the next frame's filters can reach are no longer needed (only a call that
+        # emits trims: _emit returns before that when it has no frame)
+        keep_from = np.where(k > 0, np.maximum(tail_at, self._start(next_done, 0) - (self.M - 1)), tail_at)
+        new_carry = keep_from - tail_at
+        step = dict(
+            carry_len=c, avail=avail, k=k, start=self._start(done, tail_at), new_carry=new_carry,
+            next_done=next_done, next_waiting=waiting - k * S, next_skip_left=skip_left, next_tail_at=keep_from,
+            next_carry_len=avail - new_carry,
+            word=word, next_word=(word ^ 1) | (lengths > 0) * _HAS_SAMPLE,
+        )
+        assert (new_carry >= 0).all() and (new_carry <= avail).all()
+        assert (step["next_carry_len"] < self.row_length).all()
+        return step
+
+    def commit_chunks(self, ids: np.ndarray, step: dict) -> None:
+        self.done[ids] = step["next_done"]
+        self.waiting[ids] = step["next_waiting"]
+        self.skip_left[ids] = step["next_skip_left"]
+        self.tail_at[ids] = step["next_tail_at"]
+        self.carry_len[ids] = step["next_carry_len"]
+        self.started[ids] = True
+        # (the assemble kernel wrote the new carries and previous samples to the other half)
+        self.word[ids] = step["next_word"]
+
+    def tail_frames(self, waiting: np.ndarray, skip_left: np.ndarray) -> np.ndarray:
+        """``ShortIntegrationFrameComputer._tail_frames`` over arrays: frames ``finalize`` adds"""
+        S = self.S
+        borrowed = S if self.centered else 0
+        buf_len = self.translation - skip_left + waiting - borrowed
+        want = np.maximum(0, (buf_len + S // 2) // S)
+        pad_right = (want - 1) * S + self.frame_length - buf_len
+        pad_raw = pad_right - np.minimum(skip_left, pad_right)
+        return np.where(want < 1, 0, np.minimum(want, np.maximum(0, (waiting + pad_raw) // S - 1))).astype(np.int64)
+
+    def finalize_step(self, ids: np.ndarray) -> dict:
+        """What ``finalize`` does: frames `k` from the carry (`carry_len` samples in pool `half`) at `start`; none for
+        a stream that was not started"""
+        started = self.started[ids]
+        k = np.where(started, self.tail_frames(self.waiting[ids], self.skip_left[ids]), 0)
+        return dict(carry_len=self.carry_len[ids], k=k, start=self._start(self.done[ids], self.tail_at[ids]),
+                    half=self.word[ids] & 1)
+
+    def reset(self, ids: np.ndarray) -> None:
+        self.done[ids] = 0
+        self.waiting[ids] = 0
+        self.skip_left[ids] = 0
+        self.tail_at[ids] = 0
+        self.carry_len[ids] = 0
+        self.started[ids] = False
+        self.word[ids] &= 1
+
+
+class SiStreamBatch(_TickBatch):
+    """``compute_chunk`` / ``finalize`` of many streams of one short-integration computer, one tick per call
+
+    `computer`: a :class:`si.ShortIntegrationFrameComputer` (its plan and configuration are used; its own streaming
+    state is not touched).  `capacity`, `dtype`, `deltas`, `preemphasis` and every method: as
+    :class:`multistream.StreamBatch`.  Device memory: the carry pool, ``2 * capacity * row_length`` samples with
+    ``row_length = max(max_support - 1, skip0) + 2 * frame_shift`` (:attr:`SiStreamState.row_length`), plus what
+    `deltas` and `preemphasis` add there, and per tick the work buffer and, for float32 with the overlap-save form, its
+    scratch (``pds_si_scratch_len`` of the tick's streams and its largest frame count).
+    """
+
+    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None):
+        if not isinstance(computer, ShortIntegrationFrameComputer):
+            raise TypeError("SiStreamBatch serves short-integration frame computers (multistream.StreamBatch serves "
+                            "STFT ones)")
+        dtype, spec, coeff = self._check_args(dtype, deltas, preemphasis)
+        torch = _native.require_device()
+        self.state = SiStreamState.of(computer, capacity)
+        self._setup(torch, computer, self.state.row_length, dtype, spec, coeff)
+        self._batch = self._lib.pds_si_batch_starts_f32 if dtype == np.float32 else self._lib.pds_si_batch_starts_f64
+
+    # ---- a tick ---------------------------------------------------------------------
+
+    def _si_launch(self, signal, d_lm, k, R):
+        """the frames of a tick: one pds_si_batch_starts call over the streams of `d_lm`, the device int64[5, E] of their
+        offsets in `signal`, lengths, frame counts `k` (host copy), first rows and starts; more than one call only
+        beyond the utterances a call takes"""
+        torch = self._torch
+        lib = self._lib
+        feats = torch.empty((R, self._F), dtype=self._tdtype, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        E = len(k)
+        for lo in range(0, E, _MAX_UTTS_PER_CALL):
+            hi = min(E, lo + _MAX_UTTS_PER_CALL)
+            most = int(k[lo:hi].max())
+            args = (self._plan.handle, signal.data_ptr()) + tuple(d_lm[r, lo:].data_ptr() for r in range(5)) + (
+                hi - lo, most)
+            if self.dtype == np.float64:
+                rc = self._batch(*args, feats.data_ptr(), feats.stride(0), stream)
+            else:
+                # the overlap-save form when the plan has it (it needs scratch memory), else direct filtering: the
+                # choice of ShortIntegrationFrameComputer._launch
+                need = int(lib.pds_si_scratch_len(self._plan.handle, hi - lo, most))
+                scratch = torch.empty(need, dtype=torch.float32, device=self.device) if need else None
+                rc = self._batch(*args, scratch.data_ptr() if need else None, feats.data_ptr(), feats.stride(0),
+                                 stream)
+            _native.check(rc, "pds_si_batch_starts")
+        return feats
+
+    def _chunks_tick(self, ids, lengths, host_chunks=None, d_samples=None, i16=False):
+        st = self.state
+        step = st.chunk_step(ids, lengths)
+        n = len(ids)
+        avail, k = step["avail"], step["k"]
+        work_off = _exclusive_cumsum(avail)
+        rows = _exclusive_cumsum(k)
+        R = int(rows[-1])
+        tile_prefix = _exclusive_cumsum((avail + self._tile - 1) // self._tile)
+        emit = np.flatnonzero(k > 0)
+        E = len(emit)
+        # upload: [samples][assemble metadata n x 8][tile prefix n + 1][launch metadata 5 x E], int64 words, and with
+        # deltas [deltas metadata n x 8][element prefix n + 1] behind them
+        total = int(lengths.sum())
+        ns = (total * self.dtype.itemsize + 7) // 8 if host_chunks is not None else 0
+        rest = _FIELDS * n + (n + 1) + 5 * E
+        dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
+        slot, buf = self._staging(ns + rest + dwords)
+        host = buf.numpy()
+        if ns:
+            ns, i16 = self._pack_chunks(host, host_chunks, lengths, total)
+        words = ns + rest
+        if dwords:
+            dstep, elems = self._delta_meta(host[words : words + dwords], ids, k, rows[:-1], final=False)
+        am = host[ns : ns + _FIELDS * n].reshape(n, _FIELDS)
+        am[:, 0] = ids
+        am[:, 1] = _exclusive_cumsum(lengths)[:-1]
+        am[:, 2] = lengths
+        am[:, 3] = step["carry_len"]
+        am[:, 4] = 0  # (nothing of a chunk is dropped)
+        am[:, 5] = step["new_carry"]
+        am[:, 6] = work_off[:-1]
+        am[:, 7] = step["word"]
+        at = ns + _FIELDS * n
+        host[at : at + n + 1] = tile_prefix
+        lm = host[at + n + 1 : words].reshape(5, E)
+        lm[0], lm[1], lm[2], lm[3], lm[4] = work_off[:-1][emit], avail[emit], k[emit], rows[:-1][emit], step["start"][emit]
+        dev = self._send(slot, words + dwords)
+        samples = dev[:ns] if host_chunks is not None else d_samples  # (only its address is used)
+        work = self._assemble_launch(samples if total else None, i16, dev[ns:], dev[at:], n, int(tile_prefix[-1]),
+                                     int(work_off[-1]))
+        feats = self._si_launch(work, dev[at + n + 1 : words].view(5, E), k[emit], R)
+        st.commit_chunks(ids, step)
+        if dwords:
+            return self._delta_launch(feats, dev[words : words + dwords], ids, dstep, elems)
+        return feats, rows
+
+    def _finalize_tick(self, ids) -> Tuple[object, np.ndarray]:
+        st = self.state
+        step = st.finalize_step(ids)
+        c, k = step["carry_len"], step["k"]
+        rows = _exclusive_cumsum(k)
+        R = int(rows[-1])
+        offsets = (step["half"] * self.capacity + ids) * self._row_length  # the carries where they lie in the pool
+        emit = np.flatnonzero(k > 0)
+        E = len(emit)
+        n = len(ids)
+        dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
+        slot, buf = self._staging(5 * E + dwords)
+        lm = buf.numpy()[: 5 * E].reshape(5, E)
+        lm[0], lm[1], lm[2], lm[3], lm[4] = offsets[emit], c[emit], k[emit], rows[:-1][emit], step["start"][emit]
+        if dwords:
+            dstep, elems = self._delta_meta(buf.numpy()[5 * E : 5 * E + dwords], ids, k, rows[:-1], final=True)
+        dev = self._send(slot, 5 * E + dwords)
+        feats = self._si_launch(self._pool.view(-1), dev[: 5 * E].view(5, E), k[emit], R)
+        st.reset(ids)
+        if dwords:
+            return self._delta_launch(feats, dev[5 * E : 5 * E + dwords], ids, dstep, elems)
+        return feats, rows

@@ -2,7 +2,7 @@
 """Per-tick wall time of batched streaming (multistream.StreamBatch) against a loop of single-stream compute_chunk calls.
 
     python tools/stream_rate.py [--streams 64,1024,8192] [--ticks 200] [--loop 64,256] [--deltas]
-                                [--samples {f32,i16}] [--preemph C] > profiles/<tag>_stream_rate.txt
+                                [--samples {f32,i16}] [--preemph C] [--si] > profiles/<tag>_stream_rate.txt
 
 Configuration c1_readme_fbank of tests/golden/configs.json (16 kHz, 25 ms frames, 10 ms shift), 160-sample (10 ms)
 float32 chunks.  Per stream count S: `ticks` timed ticks after 20 untimed ones, each ending in a synchronisation --
@@ -13,6 +13,11 @@ through StreamBatch(deltas=Deltas(2)) (rows "host+d" / "packed+d": statics + del
 download), and no loop.  --samples i16: the chunks are 16-bit PCM, int16 arrays on the host (two bytes per sample over
 the link) and an int16 tensor on the GPU; --preemph C: StreamBatch(preemphasis=C), the pre-emphasis carried across
 ticks in the assemble launch.  Either leaves the loop out (a single-stream compute_chunk has no counterpart to them).
+
+--si: the short-integration computer instead (multistream_si.SiStreamBatch, configuration s1_gabor_mel of
+tests/golden/si_configs.json: 16 kHz, 10 ms shift), 1024 and 8192 streams by default, against the loop of
+ShortIntegrationFrameComputer.compute_chunk calls over the same chunks at 1024 streams (extrapolated to the larger
+counts by its cost per call); the ratios are reported, none is asserted.
 """
 import argparse
 import json
@@ -32,23 +37,31 @@ def pct(xs, q):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", default="64,1024,8192")
+    ap.add_argument("--streams", default=None, help="default: 64,1024,8192 (--si: 1024,8192)")
     ap.add_argument("--ticks", type=int, default=200)
-    ap.add_argument("--loop", default="64,256")
+    ap.add_argument("--loop", default=None, help="default: 64,256 (--si: 1024)")
     ap.add_argument("--loop-ticks", type=int, default=20)
     ap.add_argument("--deltas", action="store_true", help="also time the ticks with deltas=Deltas(2); skips the loop")
     ap.add_argument("--samples", choices=("f32", "i16"), default="f32", help="sample type of the chunks")
     ap.add_argument("--preemph", type=float, default=0.0, metavar="C", help="pre-emphasis coefficient (0: none)")
+    ap.add_argument("--si", action="store_true", help="short-integration streams (SiStreamBatch, s1_gabor_mel)")
     args = ap.parse_args()
+    if args.streams is None:
+        args.streams = "1024,8192" if args.si else "64,1024,8192"
+    if args.loop is None:
+        args.loop = "1024" if args.si else "64,256"
     import torch
 
     import pydrobert_speech_amd as ps
     from pydrobert_speech_amd.alias import alias_factory_subclass_from_arg
     from pydrobert_speech_amd.multistream import StreamBatch
+    from pydrobert_speech_amd.multistream_si import SiStreamBatch
     from pydrobert_speech_amd.post import Deltas
 
-    with open(os.path.join(ROOT, "tests", "golden", "configs.json")) as fh:
-        cfg = json.load(fh)["configs"]["c1_readme_fbank"]
+    name = "s1_gabor_mel" if args.si else "c1_readme_fbank"
+    Batch = SiStreamBatch if args.si else StreamBatch
+    with open(os.path.join(ROOT, "tests", "golden", "si_configs.json" if args.si else "configs.json")) as fh:
+        cfg = json.load(fh)["configs"][name]
 
     def computer():
         return alias_factory_subclass_from_arg(ps.compute.FrameComputer, json.loads(json.dumps(cfg)))
@@ -56,7 +69,7 @@ def main():
     n = 160
     chunk_ms = 1e3 * n / 16000
     rng = np.random.default_rng(0)
-    results = {"config": "c1_readme_fbank", "chunk_samples": n, "device": torch.cuda.get_device_name(0)}
+    results = {"config": name, "chunk_samples": n, "device": torch.cuda.get_device_name(0)}
     warm = 20
     variant = ""
     extra = {}
@@ -64,7 +77,7 @@ def main():
         results.update(samples=args.samples, preemph=args.preemph)
         variant = f", {args.samples} samples" + (f", preemphasis {args.preemph:g}" if args.preemph else "")
         extra = dict(preemphasis=args.preemph)
-    print(f"# {results['device']}, c1_readme_fbank, {n}-sample chunks ({chunk_ms:.0f} ms), {args.ticks} ticks{variant}")
+    print(f"# {results['device']}, {name}, {n}-sample chunks ({chunk_ms:.0f} ms), {args.ticks} ticks{variant}")
     print(f"{'streams':>8} {'api':>8} {'p50 ms':>8} {'p99 ms':>8} {'x real time':>12} {'frames/tick':>11}")
     for S in [int(s) for s in args.streams.split(",")]:
         comp = computer()
@@ -76,7 +89,7 @@ def main():
         d_block = torch.from_numpy(block.reshape(-1)).cuda()
         lens = np.full(S, n, dtype=np.int64)
         for api in ("host", "packed") + (("host+d", "packed+d") if args.deltas else ()):
-            sb = StreamBatch(comp, capacity=S, **(dict(deltas=Deltas(2)) if api.endswith("+d") else {}), **extra)
+            sb = Batch(comp, capacity=S, **(dict(deltas=Deltas(2)) if api.endswith("+d") else {}), **extra)
             times, frames = [], 0
             for t in range(warm + args.ticks):
                 t0 = time.perf_counter()
@@ -95,7 +108,8 @@ def main():
             p50, p99 = pct(times, 50), pct(times, 99)
             results[f"{api}_{S}"] = dict(p50_ms=p50, p99_ms=p99, realtime_x=chunk_ms / p50, frames_per_tick=frames / args.ticks)
             print(f"{S:>8} {api:>8} {p50:>8.3f} {p99:>8.3f} {chunk_ms / p50:>12.1f} {frames / args.ticks:>11.1f}")
-    for S in [] if args.deltas or variant else [int(s) for s in args.loop.split(",")]:
+    loops = [int(s) for s in args.loop.split(",") if s.strip() and int(s) > 0]  # (--loop 0: none)
+    for S in [] if args.deltas or variant else loops:
         comps = [computer() for _ in range(S)]
         block = (3000 * rng.standard_normal((S, n))).astype(np.float32)
         times = []
@@ -113,7 +127,21 @@ def main():
             per_stream = p50 / S
             print(f"#   loop: {1e3 * per_stream:.1f} us per compute_chunk call")
             results[f"loop_{S}"]["us_per_call"] = 1e3 * per_stream
-    if "host_1024" in results and "loop_256" in results:
+    if args.si:
+        for L in loops:
+            if f"loop_{L}" not in results:
+                continue
+            per_call = results[f"loop_{L}"]["p50_ms"] / L
+            for S in (int(s) for s in args.streams.split(",")):
+                if f"host_{S}" in results:
+                    loop_S = per_call * S
+                    results[f"speedup_{S}_host_vs_loop"] = loop_S / results[f"host_{S}"]["p50_ms"]
+                    results[f"speedup_{S}_packed_vs_loop"] = loop_S / results[f"packed_{S}"]["p50_ms"]
+                    how = "measured" if S == L else f"extrapolated from {L}"
+                    print(f"# {S} streams: loop ({how}, {loop_S:.2f} ms) / tick: host "
+                          f"{results[f'speedup_{S}_host_vs_loop']:.1f} x, packed {results[f'speedup_{S}_packed_vs_loop']:.1f} x")
+            break
+    elif "host_1024" in results and "loop_256" in results:
         loop_1024 = results["loop_256"]["us_per_call"] * 1024 / 1e3
         results["speedup_1024_host_vs_loop"] = loop_1024 / results["host_1024"]["p50_ms"]
         results["speedup_1024_packed_vs_loop"] = loop_1024 / results["packed_1024"]["p50_ms"]
