@@ -394,6 +394,35 @@ int32_t pds_multistream_deltas_f64(const double *d_statics, double *d_hist, int6
                                    double *d_out, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * Running and global CMVN of batched streaming (StreamBatch(cmvn=...)): the reference's Standardize applied frame by
+ * frame as the statics arrive.  pds_multistream_cmvn runs once per tick, in place on the tick's statics in d_statics
+ * (rows of `coeffs` values, written by pds_stft_batch_* / pds_si_batch_starts_* on the same stream), before
+ * pds_multistream_deltas.  d_prior is double[2][coeffs], the sums and the sums of squares of previously accumulated
+ * statistics (NULL: zeros).  running != 0: every stream's running sums live in d_pool, double[capacity][2][coeffs]
+ * (stream s: sums at d_pool + (s * 2) * coeffs, sums of squares `coeffs` further; one pool, no ping-pong: a
+ * (stream, coefficient) pair is read and written by one thread of a call).  running == 0: d_pool is not used and may
+ * be NULL.  d_meta holds n entries of 8 int64:
+ *   [0] stream s   [1] flags: bit 0 fresh (the stream starts from d_prior; its pool slot is not read)
+ *   [2] first row of the stream's new statics in d_statics (row index)   [3] their number k (may be 0)
+ *   [4] count c before this call: the prior's count plus the frames the stream has accumulated (running == 0: the
+ *       prior's count, which must not be 0)   [5..7] reserved, 0
+ * and, per coefficient i, with (s1, s2) the stream's sums (fresh or running == 0: d_prior's) and x the rows in order,
+ *   running:  s1 = s1 + x;  s2 = s2 + x * x;  c = c + 1                      (running == 0: unchanged)
+ *   mean = s1 / c;  var = s2 / c - mean * mean;  norm_var: if |var| <= 1e-8 then var = 1;  scale = 1 / sqrt(var)
+ *   (norm_var == 0: scale = 1);  x = (T)(x * scale - mean * scale)
+ * in float64 (x widened first), every operation rounded separately, division and square root correctly rounded:
+ * Standardize.accumulate(x); Standardize.apply(x) of the reference bit for bit (rounded once to float for _f32).  A NaN
+ * stays in the sums, as in numpy.  With running != 0 an entry with k > 0 writes its sums back to d_pool.  Streams of
+ * one call are distinct.  d_statics may be NULL when no entry has rows.
+ * --------------------------------------------------------------------------------- */
+int32_t pds_multistream_cmvn_f32(float *d_statics, double *d_pool, int64_t capacity, int32_t coeffs,
+                                 const double *d_prior, int32_t norm_var, int32_t running, const int64_t *d_meta,
+                                 int32_t n, void *stream);
+int32_t pds_multistream_cmvn_f64(double *d_statics, double *d_pool, int64_t capacity, int32_t coeffs,
+                                 const double *d_prior, int32_t norm_var, int32_t running, const int64_t *d_meta,
+                                 int32_t n, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Pre-processors as separate passes (reference pre.py:67-149); `preemph` above fuses the
  * first one into the frame load instead.
  * pds_preemphasize: per utterance of a packed buffer (offsets/lengths as in pds_stft_batch),

@@ -191,6 +191,10 @@ SIGNATURES = {
     "pds_multistream_deltas_f64": (
         c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
                   c_int64, c_void_p, c_void_p]),
+    "pds_multistream_cmvn_f32": (
+        c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "pds_multistream_cmvn_f64": (
+        c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
     # multi-GPU gather over RCCL
     "pds_comm_unique_id": (c_int32, [c_void_p]),
     "pds_comm_init_rank": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_void_p)]),

@@ -28,6 +28,16 @@
 // fresh, hist_rows) rows, written to the other half (final: keep = 0, the stream is reset).  Work is dealt by element:
 // an entry has (rows + keep) * coeffs of them, `elem_prefix` their exclusive prefix sum, and lane g of the grid takes element g -- adjacent lanes hold adjacent coefficients of one row, whether a tick
 // brings thousands of streams one frame each or one stream thousands of frames.
+//
+// Running / global CMVN across ticks (StreamBatch(cmvn=...)): multistream_cmvn_kernel, after the feature launches of a
+// tick and before its deltas, in place on the tick's statics.  Every stream of the tick is one entry of `meta`
+// (int64[n][MC_FIELDS]); one thread per (entry, coefficient), adjacent lanes adjacent coefficients, walks the entry's
+// new rows in order: running, it adds the row to the coefficient's sums (float64: sum, sum of squares, kept per stream
+// in a pool double[capacity][2][coeffs]; a fresh stream starts from the prior table instead of reading the pool), then
+// normalises the row by the sums so far -- Standardize.accumulate(frame); Standardize.apply(frame) of the reference,
+// operation for operation; global, it normalises every row by the prior's mean and scale, computed once.  A
+// (stream, coefficient) pair belongs to one thread of the launch, which reads the pool once and writes it once, so the
+// pool needs no second half.
 #include "pds_internal.h"
 
 namespace pds {
@@ -257,6 +267,94 @@ static int32_t launch_ms_deltas(const T *d_statics, T *d_hist, int64_t capacity,
   return PDS_OK;
 }
 
+// ---- running / global CMVN across ticks -----------------------------------------------------------------------
+
+enum { MC_STREAM = 0, MC_FLAGS, MC_ROW, MC_ROWS, MC_COUNT, MC_FIELDS = 8 };
+enum { MC_FLAG_FRESH = 1 };
+constexpr int MC_THREADS = 256;
+constexpr int MC_AHEAD = 4;  // row loads in flight per thread (the sums are sequential, the loads are not)
+
+// mean and scale of one coefficient from its sums and count: Standardize._apply_vector's arithmetic (float64, every
+// operation rounded separately; fabs(var) <= 1e-8 is numpy.isclose(var, 0), false for NaN as there)
+__device__ __forceinline__ void cmvn_mean_scale(double s1, double s2, double count, bool norm_var, double &mean,
+                                                double &scale) {
+  mean = s1 / count;
+  scale = 1.0;
+  if (norm_var) {
+    double var = __dsub_rn(s2 / count, __dmul_rn(mean, mean));
+    if (fabs(var) <= 1e-8) var = 1.0;
+    scale = 1.0 / sqrt(var);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(MC_THREADS) void multistream_cmvn_kernel(
+    T *__restrict__ statics, double *__restrict__ pool, int64_t capacity, int32_t F,
+    const double *__restrict__ prior, int32_t norm_var, int32_t running, const int64_t *__restrict__ meta,
+    int64_t total) {
+  const int64_t g = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  if (g >= total) return;
+  const int64_t e = g / F;
+  const int i = (int)(g - e * F);
+  const int64_t *m = meta + e * MC_FIELDS;
+  const int64_t k = m[MC_ROWS];
+  if (k <= 0) return;  // (nothing to normalise and, the sums being unchanged, nothing to write)
+  double *sums = pool + (m[MC_STREAM] * 2) * (int64_t)F + i;  // (not touched unless running)
+  double s1, s2;
+  if (running && !(m[MC_FLAGS] & MC_FLAG_FRESH)) {
+    s1 = sums[0];
+    s2 = sums[F];
+  } else {
+    s1 = prior ? prior[i] : 0.0;
+    s2 = prior ? prior[F + i] : 0.0;
+  }
+  T *x = statics + m[MC_ROW] * (int64_t)F + i;
+  double mean, scale, shift = 0.0;
+  if (!running) {  // fixed statistics: once per thread
+    cmvn_mean_scale(s1, s2, (double)m[MC_COUNT], norm_var != 0, mean, scale);
+    shift = __dmul_rn(mean, scale);
+  }
+  int64_t count = m[MC_COUNT];
+  for (int64_t t = 0; t < k; t += MC_AHEAD) {
+    T v[MC_AHEAD];
+#pragma unroll
+    for (int u = 0; u < MC_AHEAD; ++u) v[u] = t + u < k ? x[(t + u) * (int64_t)F] : T(0);
+#pragma unroll
+    for (int u = 0; u < MC_AHEAD; ++u) {
+      if (t + u >= k) continue;
+      const double d = (double)v[u];
+      if (running) {  // accumulate(frame), then apply(frame)
+        s1 = __dadd_rn(s1, d);
+        s2 = __dadd_rn(s2, __dmul_rn(d, d));
+        ++count;
+        cmvn_mean_scale(s1, s2, (double)count, norm_var != 0, mean, scale);
+        shift = __dmul_rn(mean, scale);
+      }
+      x[(t + u) * (int64_t)F] = (T)__dsub_rn(__dmul_rn(d, scale), shift);
+    }
+  }
+  if (running) {
+    sums[0] = s1;
+    sums[F] = s2;
+  }
+}
+
+template <typename T>
+static int32_t launch_ms_cmvn(T *d_statics, double *d_pool, int64_t capacity, int32_t coeffs, const double *d_prior,
+                              int32_t norm_var, int32_t running, const int64_t *d_meta, int32_t n, void *stream) {
+  if (n < 0 || capacity < 0 || coeffs <= 0) return invalid_ms("multistream_cmvn: bad size");
+  if (n == 0) return PDS_OK;
+  const int64_t total = (int64_t)n * coeffs;
+  const int64_t blocks = (total + MC_THREADS - 1) / MC_THREADS;
+  if (blocks > 0x7fffffff) return invalid_ms("multistream_cmvn: too many elements in one call");
+  // (d_statics may be null in a tick without new rows: no entry has any then)
+  if (!d_meta || (running && !d_pool)) return invalid_ms("multistream_cmvn: null pointer");
+  hipLaunchKernelGGL(multistream_cmvn_kernel<T>, dim3((unsigned)blocks), dim3(MC_THREADS), 0, (hipStream_t)stream,
+                     d_statics, d_pool, capacity, coeffs, d_prior, norm_var, running, d_meta, total);
+  PDS_HIP(hipGetLastError());
+  return PDS_OK;
+}
+
 }  // namespace pds
 
 extern "C" {
@@ -309,6 +407,17 @@ int32_t pds_multistream_deltas_f64(const double *d_statics, double *d_hist, int6
                                    double *d_out, void *stream) {
   return pds::launch_ms_deltas<double>(d_statics, d_hist, capacity, hist_rows, coeffs, d_filts, d_filt_off, K, d_meta,
                                        d_elem_prefix, n, total_elems, d_out, stream);
+}
+
+int32_t pds_multistream_cmvn_f32(float *d_statics, double *d_pool, int64_t capacity, int32_t coeffs,
+                                 const double *d_prior, int32_t norm_var, int32_t running, const int64_t *d_meta,
+                                 int32_t n, void *stream) {
+  return pds::launch_ms_cmvn<float>(d_statics, d_pool, capacity, coeffs, d_prior, norm_var, running, d_meta, n, stream);
+}
+int32_t pds_multistream_cmvn_f64(double *d_statics, double *d_pool, int64_t capacity, int32_t coeffs,
+                                 const double *d_prior, int32_t norm_var, int32_t running, const int64_t *d_meta,
+                                 int32_t n, void *stream) {
+  return pds::launch_ms_cmvn<double>(d_statics, d_pool, capacity, coeffs, d_prior, norm_var, running, d_meta, n, stream);
 }
 
 }  // extern "C"

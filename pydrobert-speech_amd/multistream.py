@@ -12,6 +12,7 @@ samples of up to `capacity` streams in a device pool and takes every stream that
 
     sb = StreamBatch(computer, capacity=4096, deltas=Deltas(2))   # statics + delta + delta-delta, see below
     sb = StreamBatch(computer, capacity=4096, preemphasis=0.97)   # Preemphasize(0.97) over every stream's whole signal
+    sb = StreamBatch(computer, capacity=4096, cmvn=Standardize())  # running CMVN per stream, see below
 
 Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
 the same chunks: the same row counts, dtype and -- for float32 and float64 samples -- the same values bit for bit as
@@ -44,6 +45,31 @@ for a chunk's first sample, the stream's last raw sample, which a third ping-pon
 across ticks (:attr:`StreamState.has_sample` says whether there is one).  A stream's first sample after its start or
 ``finalize`` passes unchanged.  The carries hold pre-emphasised samples, so ``finalize`` needs nothing more.
 
+With `cmvn` (a :class:`post.Standardize`) every static row is standardised as it is produced, in one of the two forms
+of the reference's ``Standardize`` that do not need the whole utterance.  Per stream, with x_1, x_2, .. its static rows
+since its start or last ``finalize`` and P the ``[2, F + 1]`` statistics of the ``Standardize`` passed in (sums | count,
+sums of squares; zeros without any), in float64 and every operation rounded separately:
+
+    s1_0 = P[0, :F];  s2_0 = P[1, :F];  n_0 = P[0, F]
+    running (``cmvn_running=True``):  s1_t = s1_{t-1} + x_t;  s2_t = s2_{t-1} + x_t * x_t;  n_t = n_{t-1} + 1
+    global (``cmvn_running=False``):  s1, s2 and n stay P's
+    mean = s1_t / n_t;  var = s2_t / n_t - mean * mean
+    norm_var:  var = 1 where |var| <= 1e-8;  scale = 1 / sqrt(var)        (else scale = 1)
+    y_t = x_t * scale - mean * scale
+
+-- the reference's ``cmvn.accumulate(x_t); cmvn.apply(x_t)`` frame by frame (running: cumulative mean and variance
+normalisation, optionally seeded with prior statistics) or ``cmvn.apply(x_t)`` with fixed statistics (global), bit for
+bit; y_t is rounded to `dtype` once.  As there, a stream's first frame without a prior comes out as zeros (its
+variance is 0 and replaced by 1), a constant coefficient gives zeros, and a NaN static stays in its stream's sums until
+the ``finalize``; the reference's "0 variance" warning is not raised.  ``Standardize`` without statistics over a whole
+utterance cannot be streamed: ``cmvn_running=False`` without statistics is refused.  :class:`CmvnState` counts the
+frames per stream on the host; the device keeps every stream's running sums in a pool of ``2 * capacity * F`` float64,
+and one launch per tick (``pds_multistream_cmvn_*``), after the feature launches and before the deltas, adds the
+tick's rows to the sums and normalises them in place.  ``finalize`` normalises the last frames like any others and
+returns the stream to P.  With `deltas` the deltas are taken of the normalised statics (Kaldi's ``apply-cmvn |
+add-deltas``), so the history pool holds normalised rows and a stream's rows are ``deltas.apply(Y, axis=0)``.
+:func:`StreamBatch.cmvn_stats` returns the streams' current tables.
+
 Not thread-safe; works on the current torch stream of the device that was current at construction.
 """
 from typing import List, Optional, Sequence, Tuple
@@ -53,13 +79,16 @@ import numpy as np
 from . import _native, config
 from .alias import alias_factory_subclass_from_arg
 from .compute import PackedLayout, ShortTimeFourierTransformFrameComputer
-from .post import Deltas, PostProcessor
+from .post import Deltas, PostProcessor, Standardize
 from .pre import Preemphasize, PreProcessor
 
-__all__ = ["DeltaState", "StreamBatch", "StreamState", "streaming_deltas", "streaming_preemphasis"]
+__all__ = ["CmvnState", "DeltaState", "StreamBatch", "StreamState", "streaming_cmvn", "streaming_deltas",
+           "streaming_preemphasis"]
 
 _FIELDS = 8  # int64 per entry of pds_multistream_assemble's metadata (include/pds_amd.h)
 _DFIELDS = 8  # ... and of pds_multistream_deltas'
+_CFIELDS = 8  # ... and of pds_multistream_cmvn's
+_FLAG_FRESH = 1  # of the flags word of the cmvn metadata: the stream starts from the prior statistics
 _FLAG_FINAL = 2  # (bit 0 of the flags word is the pool half)
 _HAS_SAMPLE = 2  # of word 7 of the assemble metadata, beside the pool half in bit 0: the stream has a previous sample
 _SAMPLES_F32, _SAMPLES_F64, _SAMPLES_I16 = 0, 1, 2  # PDS_SAMPLES_* (include/pds_amd.h)
@@ -303,6 +332,93 @@ class DeltaState:
         return int(prefix[-1])
 
 
+def streaming_cmvn(cmvn, running: bool, num_coeffs: int) -> Optional[Tuple[Standardize, Optional[np.ndarray], bool]]:
+    """`cmvn` as :class:`StreamBatch` takes it -- a :class:`post.Standardize` or what
+    ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one -> ``(Standardize, prior, norm_var)`` with `prior`
+    a float64 copy of its ``[2, num_coeffs + 1]`` statistics (None without any), or None for ``cmvn=None``;
+    ``ValueError`` for anything that is no ``Standardize``, for statistics of another width, for a count that is not a
+    whole number, and for ``running=False`` without statistics: per-utterance statistics need the whole utterance,
+    which a stream does not have"""
+    if cmvn is None:
+        return None
+    try:
+        cmvn = alias_factory_subclass_from_arg(PostProcessor, cmvn)
+    except (KeyError, TypeError) as e:
+        raise ValueError(f"StreamBatch: cmvn is no post-processor ({e!r})") from None
+    if not isinstance(cmvn, Standardize):
+        raise ValueError("StreamBatch: cmvn must be a post.Standardize")
+    prior = None
+    if cmvn._stats is not None:
+        prior = np.array(cmvn._stats, dtype=np.float64)
+        if prior.ndim != 2 or prior.shape != (2, int(num_coeffs) + 1):
+            raise ValueError(f"StreamBatch: the cmvn statistics have shape {prior.shape}, the computer's "
+                             f"{num_coeffs} coefficients need (2, {int(num_coeffs) + 1})")
+        count = prior[0, -1]
+        if not (0 <= count < 2.0 ** 52 and count == np.floor(count)):
+            raise ValueError("StreamBatch: the count of the cmvn statistics must be a whole number")
+        if not count:
+            prior = None  # (Standardize.have_stats: statistics of no frame are none)
+    if prior is None and not running:
+        raise ValueError("StreamBatch: cmvn_running=False needs accumulated statistics (Standardize(rfilename=...) or "
+                         "accumulate()): per-utterance statistics need the whole utterance, which a stream does not "
+                         "have -- standardise after finalize, or use running statistics")
+    return cmvn, prior, bool(cmvn._norm_var)
+
+
+class CmvnState:
+    """Host bookkeeping of the running statistics of many streams.  Needs no device.
+
+    Per stream: ``seen`` static frames accumulated since its start or last ``finalize``; a stream that has none is
+    ``fresh``: its sums are the prior's, and its slot of the device pool is not read.  `prior_count`: the count of the
+    prior statistics (0 without any); `running`: whether frames are accumulated at all (global statistics: the count a
+    tick is given is the prior's, always).
+    """
+
+    def __init__(self, capacity: int, prior_count: int = 0, running: bool = True):
+        capacity, prior_count = int(capacity), int(prior_count)
+        if capacity <= 0 or prior_count < 0:
+            raise ValueError("capacity must be positive and the prior count not negative")
+        if not running and not prior_count:
+            raise ValueError("global statistics need a prior")
+        self.capacity, self.prior_count, self.running = capacity, prior_count, bool(running)
+        self.seen = np.zeros(capacity, dtype=np.int64)
+
+    @property
+    def fresh(self) -> np.ndarray:
+        return self.seen == 0
+
+    def counts(self, ids: np.ndarray) -> np.ndarray:
+        """the count of the streams' current statistics"""
+        seen = self.seen[ids]
+        return self.prior_count + (seen if self.running else np.zeros_like(seen))
+
+    def step(self, ids: np.ndarray, k: np.ndarray, final: bool = False) -> dict:
+        """What a tick that brings streams `ids` `k` new static frames does, without changing the state: per stream
+        the `count` before the tick, whether it is `fresh`, and the frames seen after it"""
+        k = np.asarray(k, dtype=np.int64)
+        seen = self.seen[ids]
+        return dict(k=k, count=self.counts(ids), fresh=seen == 0, next_seen=seen + k, final=bool(final))
+
+    def commit(self, ids: np.ndarray, step: dict) -> None:
+        if step["final"]:
+            self.reset(ids)  # (the next utterance on the id starts from the prior again)
+        else:
+            self.seen[ids] = step["next_seen"]
+
+    def reset(self, ids: np.ndarray) -> None:
+        self.seen[ids] = 0
+
+    def fill_meta(self, meta: np.ndarray, ids: np.ndarray, step: dict, static_rows: np.ndarray) -> None:
+        """pds_multistream_cmvn's metadata of a tick into `meta` (int64[n, 8]); `static_rows`: each stream's first row
+        in the tick's statics"""
+        meta[:, 0] = ids
+        meta[:, 1] = step["fresh"] * _FLAG_FRESH
+        meta[:, 2] = static_rows
+        meta[:, 3] = step["k"]
+        meta[:, 4] = step["count"]
+        meta[:, 5:] = 0
+
+
 class _TickBatch:
     """What :class:`StreamBatch` and :class:`multistream_si.SiStreamBatch` share: the public calls, the pools, the pinned
     staging, the assemble launch, the delta rows and the download of a tick.  A subclass sets ``state`` (its host state
@@ -310,17 +426,19 @@ class _TickBatch:
     ``_finalize_tick``."""
 
     @staticmethod
-    def _check_args(dtype, deltas, preemphasis):
-        """the constructor arguments both classes take -> ``(dtype, deltas spec, coefficient)``, before any device is
-        touched"""
+    def _check_args(dtype, deltas, preemphasis, cmvn=None, cmvn_running=True, num_coeffs=0):
+        """the constructor arguments both classes take -> ``(dtype, deltas spec, coefficient, cmvn spec)``, before any
+        device is touched"""
         dtype = np.dtype(dtype)
         if dtype not in (np.float32, np.float64):
             raise TypeError("StreamBatch: samples must be float32 or float64")
-        return dtype, streaming_deltas(deltas), streaming_preemphasis(preemphasis)
+        return (dtype, streaming_deltas(deltas), streaming_preemphasis(preemphasis),
+                streaming_cmvn(cmvn, bool(cmvn_running), num_coeffs))
 
-    def _setup(self, torch, computer, row_length: int, dtype, spec, coeff):
+    def _setup(self, torch, computer, row_length: int, dtype, spec, coeff, cspec=None, cmvn_running=True):
         """the device side: `computer`'s plan, the carry pool of ``2 * capacity * row_length`` samples, the
-        previous-sample pool (with a pre-emphasis), the staging buffers and the history pool of the deltas"""
+        previous-sample pool (with a pre-emphasis), the staging buffers, the history pool of the deltas and the pool of
+        running sums of the cmvn"""
         self._torch = torch
         self._lib = _native.lib()
         self.dtype = dtype
@@ -356,6 +474,17 @@ class _TickBatch:
             self._d_filts, self._d_filt_off = self._deltas._filters_on(self.device)
             self._deltas_fn = (self._lib.pds_multistream_deltas_f32 if dtype == np.float32
                                else self._lib.pds_multistream_deltas_f64)
+        self.cstate = self._sums = self._d_prior = self._prior = None
+        if cspec is not None:
+            self._cmvn, self._prior, self._norm_var = cspec
+            self.cstate = CmvnState(self.capacity, int(self._prior[0, -1]) if self._prior is not None else 0,
+                                    bool(cmvn_running))
+            if self._prior is not None:
+                self._d_prior = torch.from_numpy(np.ascontiguousarray(self._prior[:, :-1])).to(self.device)
+            if self.cstate.running:  # every stream's running sums (a fresh stream's slot is never read: no fill)
+                self._sums = torch.empty((self.capacity, 2, self._F), dtype=torch.float64, device=self.device)
+            self._cmvn_fn = (self._lib.pds_multistream_cmvn_f32 if dtype == np.float32
+                             else self._lib.pds_multistream_cmvn_f64)
 
     # ---- public interface -----------------------------------------------------------
 
@@ -368,6 +497,26 @@ class _TickBatch:
         """bool per stream of `ids`: between its first chunk and its ``finalize``"""
         self._check_open()
         return self.state.started[self.state.check_ids(ids)].copy()
+
+    def cmvn_stats(self, ids) -> np.ndarray:
+        """the current statistics of streams `ids` (with `cmvn`): host float64 ``[len(ids), 2, F + 1]``, each stream's
+        table as ``Standardize`` keeps it (sums | count, sums of squares | unused) -- the prior, or zeros, for a stream
+        at its start or after its ``finalize``, and for every stream under ``cmvn_running=False``.  Reads the device
+        (one synchronisation) unless every stream is fresh"""
+        self._check_open()
+        if self.cstate is None:
+            raise ValueError(f"{type(self).__name__} was built without cmvn")
+        ids = self.state.check_ids(ids)
+        F = self._F
+        out = np.zeros((len(ids), 2, F + 1), dtype=np.float64)
+        if self._prior is not None:
+            out[:] = self._prior
+        live = np.flatnonzero(~self.cstate.fresh[ids]) if self.cstate.running else np.zeros(0, dtype=np.int64)
+        if len(live):
+            at = self._torch.from_numpy(ids[live]).to(self.device)
+            out[live, :, :F] = self._sums[at].cpu().numpy()
+            out[live, 0, F] = self.cstate.counts(ids[live])
+        return out
 
     def compute_chunks(self, ids, chunks: Sequence) -> List[np.ndarray]:
         """``compute_chunk`` of ``chunks[i]`` (1-D host array) for stream ``ids[i]``; returns the list of feature
@@ -418,8 +567,8 @@ class _TickBatch:
         return self._finalize_tick(self.state.check_ids(ids))
 
     def close(self) -> None:
-        """Release the pool and the pinned buffers; the object cannot be used afterwards"""
-        self._pool = self._hist = self._prev = None
+        """Release the pools and the pinned buffers; the object cannot be used afterwards"""
+        self._pool = self._hist = self._prev = self._sums = self._d_prior = None
         self._up = [None, None]
         self._up_events = [None, None]
         self._down = None
@@ -525,6 +674,27 @@ class _TickBatch:
         self.dstate.commit(ids, dstep)
         return out, rows
 
+    def _cmvn_words(self, n: int) -> int:
+        """int64 words of the cmvn part of a tick's upload (0 without cmvn)"""
+        return _CFIELDS * n if self.cstate is not None else 0
+
+    def _cmvn_meta(self, words, ids, k, static_rows, final):
+        """the cmvn part of a tick's upload into `words` (pinned int64): the streams' step"""
+        cstep = self.cstate.step(ids, k, final=final)
+        self.cstate.fill_meta(words.reshape(len(ids), _CFIELDS), ids, cstep, static_rows)
+        return cstep
+
+    def _cmvn_launch(self, statics, d_words, ids, cstep):
+        """one pds_multistream_cmvn launch, in place over the tick's `statics` (none in a tick without new rows: no
+        stream's sums change then)"""
+        if statics.shape[0]:
+            rc = self._cmvn_fn(statics.data_ptr(), self._sums.data_ptr() if self._sums is not None else None,
+                               self.capacity, self._F, self._d_prior.data_ptr() if self._d_prior is not None else None,
+                               int(self._norm_var), int(self.cstate.running), d_words.data_ptr(), len(ids),
+                               self._torch.cuda.current_stream(self.device).cuda_stream)
+            _native.check(rc, "pds_multistream_cmvn")
+        self.cstate.commit(ids, cstep)
+
     def _to_host(self, feats, rows, started) -> List[np.ndarray]:
         """one download into pinned memory, one synchronisation, views per stream"""
         torch = self._torch
@@ -569,19 +739,32 @@ class StreamBatch(_TickBatch):
     the last ``n - e``.  Additional device memory: the history pool, exactly ``2 * capacity * 2 * H * F`` elements of
     `dtype` (two halves of ``2 H`` static rows per stream), and per tick the ``(new rows, F)`` statics.
 
+    `cmvn`: a :class:`post.Standardize` (or what ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one:
+    ``"cmvn"``, ``{"name": "cmvn", "rfilename": ...}``); ``None``: none.  With ``cmvn_running=True`` every stream's
+    static rows are standardised by the statistics of the rows so far, this one included, on top of the statistics the
+    ``Standardize`` holds, if any -- the reference's ``cmvn.accumulate(x); cmvn.apply(x)`` frame by frame, in float64,
+    rounded to `dtype` once; with ``cmvn_running=False`` by the fixed statistics it holds, which it then must
+    (``cmvn.apply(x)``).  The arithmetic, the first frame of zeros, NaN and the order with `deltas` (the deltas are
+    those of the normalised statics) are in the module docstring; the reference's "0 variance" warning is not raised.
+    The statistics' count must be a whole number.  ``finalize`` returns a stream to the statistics passed in;
+    :func:`cmvn_stats` reads a stream's current ones.  The ``Standardize`` itself is not changed.  Additional device
+    memory: the running sums, ``2 * capacity * F`` float64 (none with ``cmvn_running=False``).
+
     Under ``config.FLOAT64_ARITHMETIC == "float32"`` float64 samples are rounded to float32 once in the work buffer
     (after a pre-emphasis, which works in float64) and the float32 features widened (within the float32 tolerance of
-    the computer's path, not bit for bit).
+    the computer's path, not bit for bit); a `cmvn` then works on the widened features.
     """
 
-    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None):
+    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None, cmvn=None,
+                 cmvn_running=True):
         if not isinstance(computer, ShortTimeFourierTransformFrameComputer):
             raise TypeError("StreamBatch serves STFT frame computers (streaming short integration is not supported "
                             "here: multistream_si.SiStreamBatch serves those)")
-        dtype, spec, coeff = self._check_args(dtype, deltas, preemphasis)
+        dtype, spec, coeff, cspec = self._check_args(dtype, deltas, preemphasis, cmvn, cmvn_running,
+                                                     computer.num_coeffs)
         torch = _native.require_device()
         self.state = StreamState(capacity, computer.frame_length, computer.frame_shift, computer.pad_left)
-        self._setup(torch, computer, computer.frame_length, dtype, spec, coeff)
+        self._setup(torch, computer, computer.frame_length, dtype, spec, coeff, cspec, cmvn_running)
 
     # ---- a tick ---------------------------------------------------------------------
 
@@ -619,18 +802,21 @@ class StreamBatch(_TickBatch):
         order = emit[np.argsort(cp[emit], kind="stable")]
         E = len(order)
         # upload: [samples][assemble metadata n x 8][tile prefix n + 1][launch metadata 4 x E], int64 words, and with
-        # deltas [deltas metadata n x 8][element prefix n + 1] behind them
+        # deltas [deltas metadata n x 8][element prefix n + 1], with cmvn [cmvn metadata n x 8] behind them
         total = int(lengths.sum())
         ns = (total * self.dtype.itemsize + 7) // 8 if host_chunks is not None else 0
         rest = _FIELDS * n + (n + 1) + 4 * E
         dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
-        slot, buf = self._staging(ns + rest + dwords)
+        cwords = self._cmvn_words(n)
+        slot, buf = self._staging(ns + rest + dwords + cwords)
         host = buf.numpy()
         if ns:
             ns, i16 = self._pack_chunks(host, host_chunks, lengths, total)
         words = ns + rest
         if dwords:
             dstep, elems = self._delta_meta(host[words : words + dwords], ids, k, rows[:-1], final=False)
+        if cwords:
+            cstep = self._cmvn_meta(host[words + dwords : words + dwords + cwords], ids, k, rows[:-1], final=False)
         am = host[ns : ns + _FIELDS * n].reshape(n, _FIELDS)
         am[:, 0] = ids
         am[:, 1] = _exclusive_cumsum(lengths)[:-1]
@@ -644,13 +830,15 @@ class StreamBatch(_TickBatch):
         host[at : at + n + 1] = tile_prefix
         lm = host[at + n + 1 : words].reshape(4, E)
         lm[0], lm[1], lm[2], lm[3] = work_off[:-1][order], avail[order], k[order], rows[:-1][order]
-        dev = self._send(slot, words + dwords)
+        dev = self._send(slot, words + dwords + cwords)
         samples = dev[:ns] if host_chunks is not None else d_samples  # (only its address is used)
         work = self._assemble_launch(samples if total else None, i16, dev[ns:], dev[at:], n, int(tile_prefix[-1]),
                                      int(work_off[-1]))
         feats = self._launch_groups(work, dev[at + n + 1 : words].view(4, E), order, cp, k, work_off[:-1], avail,
                                     rows[:-1], R)
         st.commit_chunks(ids, step)
+        if cwords:
+            self._cmvn_launch(feats, dev[words + dwords :], ids, cstep)
         if dwords:
             return self._delta_launch(feats, dev[words : words + dwords], ids, dstep, elems)
         return feats, rows
@@ -667,15 +855,20 @@ class StreamBatch(_TickBatch):
         E = len(order)
         n = len(ids)
         dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
-        slot, buf = self._staging(4 * E + dwords)
+        cwords = self._cmvn_words(n)
+        slot, buf = self._staging(4 * E + dwords + cwords)
         lm = buf.numpy()[: 4 * E].reshape(4, E)
         lm[0], lm[1], lm[2], lm[3] = offsets[order], c[order], k[order], rows[:-1][order]
         if dwords:
             dstep, elems = self._delta_meta(buf.numpy()[4 * E : 4 * E + dwords], ids, k, rows[:-1], final=True)
-        dev = self._send(slot, 4 * E + dwords)
+        if cwords:
+            cstep = self._cmvn_meta(buf.numpy()[4 * E + dwords : 4 * E + dwords + cwords], ids, k, rows[:-1], final=True)
+        dev = self._send(slot, 4 * E + dwords + cwords)
         feats = self._launch_groups(self._pool.view(-1), dev[: 4 * E].view(4, E), order, cp, k, offsets, c,
                                     rows[:-1], R)
         st.reset(ids)
+        if cwords:
+            self._cmvn_launch(feats, dev[4 * E + dwords :], ids, cstep)
         if dwords:
             return self._delta_launch(feats, dev[4 * E : 4 * E + dwords], ids, dstep, elems)
         return feats, rows

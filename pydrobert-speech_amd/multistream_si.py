@@ -10,6 +10,7 @@
     sb.close()
 
     sb = SiStreamBatch(computer, capacity=4096, deltas=Deltas(2), preemphasis=0.97)   # as for StreamBatch
+    sb = SiStreamBatch(computer, capacity=4096, cmvn=Standardize(), cmvn_running=True)  # as for StreamBatch
 
 Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
 the same chunks: the same row counts, dtype and -- for float32 and float64 samples alike -- the same values bit for
@@ -21,7 +22,13 @@ Which streams a tick names, and in which order, changes no stream's result.  Chu
 values of the same chunks converted to `dtype` first (the single-stream computer refuses integer chunks; the batch
 takes them as ``StreamBatch`` does).  With `deltas` a stream's rows are ``Deltas.apply`` of its whole sequence of
 statics, delayed by :attr:`SiStreamBatch.lookahead` frames; with `preemphasis` they are those of the pre-emphasised
-whole signal; both bit for bit, as documented in :mod:`multistream`.
+whole signal; both bit for bit, as documented in :mod:`multistream`.  With `cmvn` (a :class:`post.Standardize`) every
+static row is standardised as it is produced: running (``cmvn_running=True``), the reference's ``cmvn.accumulate(x);
+cmvn.apply(x)`` frame by frame -- cumulative mean and variance normalisation, on top of the statistics passed in, if
+any -- or global (``cmvn_running=False``), ``cmvn.apply(x)`` with those fixed statistics; float64, bit for bit, rounded
+to `dtype` once; a stream's first frame without a prior is a row of zeros, a NaN stays in its stream's sums until the
+``finalize``, the reference's "0 variance" warning is not raised, and deltas are taken of the normalised statics.  The
+arithmetic is spelled out in :mod:`multistream`.
 
 A tick: :class:`SiStreamState` -- the array form of ``si.py``'s ``compute_chunk`` / ``_emit`` / ``finalize``
 bookkeeping -- is advanced on the host, which fixes every size without reading the device; samples and metadata go up
@@ -29,8 +36,8 @@ in one copy from pinned memory; one ``pds_multistream_assemble_*`` launch writes
 + chunk of every stream) and the new carries into the other pool half; one ``pds_si_batch_starts_*`` call computes
 the frames of every stream that has any, each continued at its own `start` (float32: the plan's overlap-save form
 when it has one, else direct filtering; float64: direct filtering -- the choices the single-stream computer makes);
-optionally one ``pds_multistream_deltas_*`` launch; one download.  ``finalize`` reads the carries where they lie in
-the pool.
+optionally one ``pds_multistream_cmvn_*`` launch and one ``pds_multistream_deltas_*`` launch, in that order; one
+download.  ``finalize`` reads the carries where they lie in the pool.
 
 The per-utterance start is what makes one call enough.  A stream's `start` is ``skip0 - lead + done * S - tail_at``:
 the position of its next frame's first integrated sample, relative to the first sample it still keeps.  Once
@@ -181,21 +188,25 @@ class SiStreamBatch(_TickBatch):
     """``compute_chunk`` / ``finalize`` of many streams of one short-integration computer, one tick per call
 
     `computer`: a :class:`si.ShortIntegrationFrameComputer` (its plan and configuration are used; its own streaming
-    state is not touched).  `capacity`, `dtype`, `deltas`, `preemphasis` and every method: as
-    :class:`multistream.StreamBatch`.  Device memory: the carry pool, ``2 * capacity * row_length`` samples with
-    ``row_length = max(max_support - 1, skip0) + 2 * frame_shift`` (:attr:`SiStreamState.row_length`), plus what
-    `deltas` and `preemphasis` add there, and per tick the work buffer and, for float32 with the overlap-save form, its
+    state is not touched).  `capacity`, `dtype`, `deltas`, `preemphasis`, `cmvn`, `cmvn_running` and every method
+    (``cmvn_stats`` among them): as :class:`multistream.StreamBatch` -- with `cmvn` the static rows are standardised
+    frame by frame, running or by fixed statistics, before the deltas are taken.  Device memory: the carry pool,
+    ``2 * capacity * row_length`` samples with ``row_length = max(max_support - 1, skip0) + 2 * frame_shift``
+    (:attr:`SiStreamState.row_length`), plus what `deltas`, `preemphasis` and `cmvn` (the running sums,
+    ``2 * capacity * F`` float64) add there, and per tick the work buffer and, for float32 with the overlap-save form, its
     scratch (``pds_si_scratch_len`` of the tick's streams and its largest frame count).
     """
 
-    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None):
+    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None, cmvn=None,
+                 cmvn_running=True):
         if not isinstance(computer, ShortIntegrationFrameComputer):
             raise TypeError("SiStreamBatch serves short-integration frame computers (multistream.StreamBatch serves "
                             "STFT ones)")
-        dtype, spec, coeff = self._check_args(dtype, deltas, preemphasis)
+        dtype, spec, coeff, cspec = self._check_args(dtype, deltas, preemphasis, cmvn, cmvn_running,
+                                                     computer.num_coeffs)
         torch = _native.require_device()
         self.state = SiStreamState.of(computer, capacity)
-        self._setup(torch, computer, self.state.row_length, dtype, spec, coeff)
+        self._setup(torch, computer, self.state.row_length, dtype, spec, coeff, cspec, cmvn_running)
         self._batch = self._lib.pds_si_batch_starts_f32 if dtype == np.float32 else self._lib.pds_si_batch_starts_f64
 
     # ---- a tick ---------------------------------------------------------------------
@@ -238,18 +249,21 @@ class SiStreamBatch(_TickBatch):
         emit = np.flatnonzero(k > 0)
         E = len(emit)
         # upload: [samples][assemble metadata n x 8][tile prefix n + 1][launch metadata 5 x E], int64 words, and with
-        # deltas [deltas metadata n x 8][element prefix n + 1] behind them
+        # deltas [deltas metadata n x 8][element prefix n + 1], with cmvn [cmvn metadata n x 8] behind them
         total = int(lengths.sum())
         ns = (total * self.dtype.itemsize + 7) // 8 if host_chunks is not None else 0
         rest = _FIELDS * n + (n + 1) + 5 * E
         dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
-        slot, buf = self._staging(ns + rest + dwords)
+        cwords = self._cmvn_words(n)
+        slot, buf = self._staging(ns + rest + dwords + cwords)
         host = buf.numpy()
         if ns:
             ns, i16 = self._pack_chunks(host, host_chunks, lengths, total)
         words = ns + rest
         if dwords:
             dstep, elems = self._delta_meta(host[words : words + dwords], ids, k, rows[:-1], final=False)
+        if cwords:
+            cstep = self._cmvn_meta(host[words + dwords : words + dwords + cwords], ids, k, rows[:-1], final=False)
         am = host[ns : ns + _FIELDS * n].reshape(n, _FIELDS)
         am[:, 0] = ids
         am[:, 1] = _exclusive_cumsum(lengths)[:-1]
@@ -263,12 +277,14 @@ class SiStreamBatch(_TickBatch):
         host[at : at + n + 1] = tile_prefix
         lm = host[at + n + 1 : words].reshape(5, E)
         lm[0], lm[1], lm[2], lm[3], lm[4] = work_off[:-1][emit], avail[emit], k[emit], rows[:-1][emit], step["start"][emit]
-        dev = self._send(slot, words + dwords)
+        dev = self._send(slot, words + dwords + cwords)
         samples = dev[:ns] if host_chunks is not None else d_samples  # (only its address is used)
         work = self._assemble_launch(samples if total else None, i16, dev[ns:], dev[at:], n, int(tile_prefix[-1]),
                                      int(work_off[-1]))
         feats = self._si_launch(work, dev[at + n + 1 : words].view(5, E), k[emit], R)
         st.commit_chunks(ids, step)
+        if cwords:
+            self._cmvn_launch(feats, dev[words + dwords :], ids, cstep)
         if dwords:
             return self._delta_launch(feats, dev[words : words + dwords], ids, dstep, elems)
         return feats, rows
@@ -284,14 +300,19 @@ class SiStreamBatch(_TickBatch):
         E = len(emit)
         n = len(ids)
         dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
-        slot, buf = self._staging(5 * E + dwords)
+        cwords = self._cmvn_words(n)
+        slot, buf = self._staging(5 * E + dwords + cwords)
         lm = buf.numpy()[: 5 * E].reshape(5, E)
         lm[0], lm[1], lm[2], lm[3], lm[4] = offsets[emit], c[emit], k[emit], rows[:-1][emit], step["start"][emit]
         if dwords:
             dstep, elems = self._delta_meta(buf.numpy()[5 * E : 5 * E + dwords], ids, k, rows[:-1], final=True)
-        dev = self._send(slot, 5 * E + dwords)
+        if cwords:
+            cstep = self._cmvn_meta(buf.numpy()[5 * E + dwords : 5 * E + dwords + cwords], ids, k, rows[:-1], final=True)
+        dev = self._send(slot, 5 * E + dwords + cwords)
         feats = self._si_launch(self._pool.view(-1), dev[: 5 * E].view(5, E), k[emit], R)
         st.reset(ids)
+        if cwords:
+            self._cmvn_launch(feats, dev[5 * E + dwords :], ids, cstep)
         if dwords:
             return self._delta_launch(feats, dev[5 * E : 5 * E + dwords], ids, dstep, elems)
         return feats, rows

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-tick wall time of batched streaming (multistream.StreamBatch) against a loop of single-stream compute_chunk calls.
 
-    python tools/stream_rate.py [--streams 64,1024,8192] [--ticks 200] [--loop 64,256] [--deltas]
+    python tools/stream_rate.py [--streams 64,1024,8192] [--ticks 200] [--loop 64,256] [--deltas] [--cmvn]
                                 [--samples {f32,i16}] [--preemph C] [--si] > profiles/<tag>_stream_rate.txt
 
 Configuration c1_readme_fbank of tests/golden/configs.json (16 kHz, 25 ms frames, 10 ms shift), 160-sample (10 ms)
@@ -10,7 +10,9 @@ compute_chunks (host arrays in, host arrays out) and compute_chunks_packed (samp
 there).  Real-time headroom = chunk duration / p50 tick.  The loop: compute_chunk of one chunk on each of S
 single-stream computers per tick (the host feed path, as a caller gets it).  --deltas: the same ticks once more
 through StreamBatch(deltas=Deltas(2)) (rows "host+d" / "packed+d": statics + delta + delta-delta, three times the
-download), and no loop.  --samples i16: the chunks are 16-bit PCM, int16 arrays on the host (two bytes per sample over
+download), and no loop.  --cmvn: the same ticks once more through StreamBatch(cmvn=Standardize()), running mean and
+variance normalisation per stream (rows "host+c" / "packed+c": one more launch per tick, the same download), and no
+loop.  --samples i16: the chunks are 16-bit PCM, int16 arrays on the host (two bytes per sample over
 the link) and an int16 tensor on the GPU; --preemph C: StreamBatch(preemphasis=C), the pre-emphasis carried across
 ticks in the assemble launch.  Either leaves the loop out (a single-stream compute_chunk has no counterpart to them).
 
@@ -42,6 +44,7 @@ def main():
     ap.add_argument("--loop", default=None, help="default: 64,256 (--si: 1024)")
     ap.add_argument("--loop-ticks", type=int, default=20)
     ap.add_argument("--deltas", action="store_true", help="also time the ticks with deltas=Deltas(2); skips the loop")
+    ap.add_argument("--cmvn", action="store_true", help="also time the ticks with cmvn=Standardize(); skips the loop")
     ap.add_argument("--samples", choices=("f32", "i16"), default="f32", help="sample type of the chunks")
     ap.add_argument("--preemph", type=float, default=0.0, metavar="C", help="pre-emphasis coefficient (0: none)")
     ap.add_argument("--si", action="store_true", help="short-integration streams (SiStreamBatch, s1_gabor_mel)")
@@ -56,7 +59,7 @@ def main():
     from pydrobert_speech_amd.alias import alias_factory_subclass_from_arg
     from pydrobert_speech_amd.multistream import StreamBatch
     from pydrobert_speech_amd.multistream_si import SiStreamBatch
-    from pydrobert_speech_amd.post import Deltas
+    from pydrobert_speech_amd.post import Deltas, Standardize
 
     name = "s1_gabor_mel" if args.si else "c1_readme_fbank"
     Batch = SiStreamBatch if args.si else StreamBatch
@@ -88,8 +91,10 @@ def main():
         ids = np.arange(S)
         d_block = torch.from_numpy(block.reshape(-1)).cuda()
         lens = np.full(S, n, dtype=np.int64)
-        for api in ("host", "packed") + (("host+d", "packed+d") if args.deltas else ()):
-            sb = Batch(comp, capacity=S, **(dict(deltas=Deltas(2)) if api.endswith("+d") else {}), **extra)
+        apis = ("host", "packed") + (("host+d", "packed+d") if args.deltas else ())
+        for api in apis + (("host+c", "packed+c") if args.cmvn else ()):
+            post = dict(deltas=Deltas(2)) if api.endswith("+d") else dict(cmvn=Standardize()) if api.endswith("+c") else {}
+            sb = Batch(comp, capacity=S, **post, **extra)
             times, frames = [], 0
             for t in range(warm + args.ticks):
                 t0 = time.perf_counter()
@@ -109,7 +114,7 @@ def main():
             results[f"{api}_{S}"] = dict(p50_ms=p50, p99_ms=p99, realtime_x=chunk_ms / p50, frames_per_tick=frames / args.ticks)
             print(f"{S:>8} {api:>8} {p50:>8.3f} {p99:>8.3f} {chunk_ms / p50:>12.1f} {frames / args.ticks:>11.1f}")
     loops = [int(s) for s in args.loop.split(",") if s.strip() and int(s) > 0]  # (--loop 0: none)
-    for S in [] if args.deltas or variant else loops:
+    for S in [] if args.deltas or args.cmvn or variant else loops:
         comps = [computer() for _ in range(S)]
         block = (3000 * rng.standard_normal((S, n))).astype(np.float32)
         times = []
