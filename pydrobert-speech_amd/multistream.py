@@ -28,6 +28,14 @@ kernels run over the work buffer with explicit per-stream frame counts, one laun
 reflection is launch-wide; in steady state every stream has pad 0); features come down in one copy.  ``finalize``
 reads the carries where they lie in the pool.
 
+Both kinds of tick, of this class and of :class:`multistream_si.SiStreamBatch`, are one pipeline,
+:func:`_TickBatch._tick`: the streams' spans (where each one's samples lie in what the feature launch reads), the
+upload -- laid out by :func:`_tick_layout` and addressed by section name through :class:`_Upload`, nowhere by hand --,
+the assemble launch (``compute_chunks`` only), the feature launch, the commit or reset of the host state, then the
+cmvn and the deltas launch.  A class adds what differs through four hooks: its host state, the order in which the
+emitting streams launch, its extra rows of launch metadata, and the feature launch itself.  A new stage is one edit
+there.
+
 With `deltas` (a :class:`post.Deltas`: "edge" padding, concatenated along the coefficient axis) a stream's rows are
 those of ``deltas.apply(X, axis=0)`` over the whole sequence X of its statics, bit for bit, delayed by the look-ahead
 ``H = num_deltas * context_window`` frames a delta row needs of the future: a ``compute_chunks`` call returns the rows
@@ -72,6 +80,7 @@ add-deltas``), so the history pool holds normalised rows and a stream's rows are
 
 Not thread-safe; works on the current torch stream of the device that was current at construction.
 """
+import functools
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -101,29 +110,18 @@ def _exclusive_cumsum(x: np.ndarray) -> np.ndarray:
     return out
 
 
-class StreamState:
-    """Host bookkeeping of many streams: the state machine of ``compute_chunk`` / ``finalize`` (compute.py) applied to
-    arrays of streams.  Needs no device.
+class _StreamWords:
+    """What the host states of both stream batches keep alike, per stream: ``started`` between the first chunk and
+    ``finalize``, and one ``word`` as the assemble metadata takes it -- bit 0 the pool ``half`` holding the carry and
+    the stream's previous sample (every tick that names the stream writes the other half), bit 1 ``has_sample``: given
+    at least one sample since its start or last reset (a pre-emphasis has a previous sample to use) -- so a tick
+    gathers and scatters the two once."""
 
-    Per stream: ``carry_len`` samples carried (always < `frame_length`), ``carry_pad`` left reflection the carry's
-    first frame still needs, ``skip`` samples still to drop (`frame_shift` > `frame_length`), ``first`` no frame
-    emitted yet, ``started`` between the first chunk and ``finalize``, ``has_sample`` given at least one sample since
-    its start or last reset (a pre-emphasis has a previous sample to use), ``half`` the pool half holding the carry --
-    and the stream's previous sample, whose pool every tick that names the stream writes too.  The last two are kept
-    as the assemble metadata takes them, in one ``word`` per stream (bit 0 the half, bit 1 the flag), so a tick gathers
-    and scatters them once.
-    """
-
-    def __init__(self, capacity: int, frame_length: int, frame_shift: int, pad_left: int):
+    def __init__(self, capacity: int):
         capacity = int(capacity)
         if capacity <= 0:
             raise ValueError("capacity must be positive")
         self.capacity = capacity
-        self.L, self.S, self.pad_left = int(frame_length), int(frame_shift), int(pad_left)
-        self.carry_len = np.zeros(capacity, dtype=np.int64)
-        self.carry_pad = np.full(capacity, self.pad_left, dtype=np.int64)
-        self.skip = np.zeros(capacity, dtype=np.int64)
-        self.first = np.ones(capacity, dtype=bool)
         self.started = np.zeros(capacity, dtype=bool)
         self.word = np.zeros(capacity, dtype=np.int64)
 
@@ -134,6 +132,11 @@ class StreamState:
     @property
     def has_sample(self) -> np.ndarray:
         return (self.word & _HAS_SAMPLE) != 0
+
+    @staticmethod
+    def next_word(word: np.ndarray, lengths: np.ndarray) -> np.ndarray:
+        """the words after a tick that brought the streams chunks of `lengths`"""
+        return (word ^ 1) | (lengths > 0) * _HAS_SAMPLE
 
     def check_ids(self, ids) -> np.ndarray:
         """`ids` as int64, or ``ValueError`` if any is unknown, negative or repeated"""
@@ -150,6 +153,25 @@ class StreamState:
         if np.unique(arr).size != arr.size:
             raise ValueError("a tick names each stream at most once")
         return arr
+
+
+class StreamState(_StreamWords):
+    """Host bookkeeping of many streams: the state machine of ``compute_chunk`` / ``finalize`` (compute.py) applied to
+    arrays of streams.  Needs no device.
+
+    Per stream: ``carry_len`` samples carried (always < `frame_length`), ``carry_pad`` left reflection the carry's
+    first frame still needs, ``skip`` samples still to drop (`frame_shift` > `frame_length`), ``first`` no frame
+    emitted yet, and ``started``, ``has_sample`` and ``half`` as :class:`_StreamWords` keeps them.
+    """
+
+    def __init__(self, capacity: int, frame_length: int, frame_shift: int, pad_left: int):
+        super().__init__(capacity)
+        capacity = self.capacity
+        self.L, self.S, self.pad_left = int(frame_length), int(frame_shift), int(pad_left)
+        self.carry_len = np.zeros(capacity, dtype=np.int64)
+        self.carry_pad = np.full(capacity, self.pad_left, dtype=np.int64)
+        self.skip = np.zeros(capacity, dtype=np.int64)
+        self.first = np.ones(capacity, dtype=bool)
 
     def chunk_step(self, ids: np.ndarray, lengths: np.ndarray) -> dict:
         """What ``compute_chunk`` of chunks of `lengths` does to streams `ids` (compute.py ``compute_chunk``), without
@@ -174,7 +196,7 @@ class StreamState:
             next_cp=np.where(fwd, 0, np.where(emit, -nxt, cp)),
             next_first=self.first[ids] & ~emit,
             next_carry_len=avail - new_carry,
-            word=word, next_word=(word ^ 1) | (lengths > 0) * _HAS_SAMPLE,
+            word=word, next_word=self.next_word(word, lengths),
         )
         assert (step["next_carry_len"] < L).all()
         return step
@@ -419,26 +441,95 @@ class CmvnState:
         meta[:, 5:] = 0
 
 
-class _TickBatch:
-    """What :class:`StreamBatch` and :class:`multistream_si.SiStreamBatch` share: the public calls, the pools, the pinned
-    staging, the assemble launch, the delta rows and the download of a tick.  A subclass sets ``state`` (its host state
-    machine: ``check_ids``, ``started``), then calls :func:`_setup`, and implements ``_chunks_tick`` and
-    ``_finalize_tick``."""
+class _Upload:
+    """A tick's one upload, in int64 words: `sample_words` of samples, then the sections of `layout`
+    (:func:`_place`) back to back.  `words` is the sum: what the tick asks of the staging and what it sends.  The
+    sections are placed relative to the end of the samples, so `sample_words` may still be lowered after the staging
+    was asked (a tick that travels as int16 takes fewer words than its size in `dtype`).  ``host(name)`` / ``dev(name)``
+    are the views of a section (or of ``"samples"``), in its shape, of `pinned` (the staging buffer's words, a numpy
+    array) and of `device` (the tensor :func:`_TickBatch._send` returns); an empty section has valid empty views."""
 
-    @staticmethod
-    def _check_args(dtype, deltas, preemphasis, cmvn=None, cmvn_running=True, num_coeffs=0):
-        """the constructor arguments both classes take -> ``(dtype, deltas spec, coefficient, cmvn spec)``, before any
-        device is touched"""
+    def __init__(self, sample_words, layout):
+        self.sample_words = sample_words
+        self.at, self.section_words = layout
+        self.pinned = self.device = None
+
+    @property
+    def words(self):
+        return self.sample_words + self.section_words
+
+    def host(self, name):
+        if name == "samples":
+            return self.pinned[: self.sample_words]
+        lo, size, shape, _ = self.at[name]
+        lo += self.sample_words
+        return self.pinned[lo : lo + size].reshape(shape)
+
+    def dev(self, name):
+        if name == "samples":
+            return self.device[: self.sample_words]
+        lo, _, shape, strides = self.at[name]
+        # (`device` is a whole tensor: its storage starts at its word 0)
+        return self.device.as_strided(shape, strides, self.sample_words + lo)
+
+
+def _place(sections):
+    """`sections` -- ``(name, shape)`` with one- or two-dimensional shapes, in int64 words -- back to back in the order
+    given -> ``({name: (first word, words, shape, strides)}, words of all)``.  A section that a tick does not have has a
+    zero in its shape and takes no words"""
+    at = {}
+    off = 0
+    for name, shape in sections:
+        if len(shape) == 2:
+            size, strides = shape[0] * shape[1], (shape[1], 1)
+        else:
+            size, strides = shape[0], (1,)
+        at[name] = (off, size, shape, strides)
+        off += size
+    return at, off
+
+
+@functools.lru_cache(maxsize=256)  # (a batch's ticks repeat a few sizes: each is placed once)
+def _tick_layout(n, E, launch_rows, chunks, deltas, cmvn):
+    """The sections behind the samples in the upload of a tick over `n` streams of which `E` emit frames, placed: the
+    assemble metadata and the tile prefix (`chunks`: a ``compute_chunks`` tick; ``finalize`` has neither, and no
+    samples), the launch metadata -- `launch_rows` rows, one column per emitting stream --, the deltas metadata and
+    the element prefix (`deltas`), the cmvn metadata (`cmvn`)"""
+    return _place((("assemble", (n if chunks else 0, _FIELDS)),
+                   ("tiles", (n + 1 if chunks else 0,)),
+                   ("launch", (launch_rows, E)),
+                   ("deltas", (n if deltas else 0, _DFIELDS)),
+                   ("elems", (n + 1 if deltas else 0,)),
+                   ("cmvn", (n if cmvn else 0, _CFIELDS))))
+
+
+class _TickBatch:
+    """What :class:`StreamBatch` and :class:`multistream_si.SiStreamBatch` share: the constructor, the public calls, the
+    pools, the pinned staging and -- :func:`_tick` -- the one pipeline of a tick, ``compute_chunks`` and ``finalize``
+    alike.  A subclass states what differs: `_computer_type` (and the ``TypeError`` message for another,
+    `_wrong_computer`), :func:`_new_state` (its host state machine -- ``chunk_step``, ``commit_chunks``,
+    ``finalize_step``, ``reset`` over a :class:`_StreamWords` -- and the row length of the carry pool),
+    :func:`_emit_order` (which order the emitting streams launch in), `_launch_extra` (the keys of a step that follow
+    offset, length, frame count and first row in the launch metadata, a row each) and :func:`_feature_launch`."""
+
+    _computer_type = _wrong_computer = None
+    _launch_extra = ()
+
+    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None, cmvn=None,
+                 cmvn_running=True):
+        # every argument is read before a device is touched
+        if not isinstance(computer, self._computer_type):
+            raise TypeError(self._wrong_computer)
         dtype = np.dtype(dtype)
         if dtype not in (np.float32, np.float64):
             raise TypeError("StreamBatch: samples must be float32 or float64")
-        return (dtype, streaming_deltas(deltas), streaming_preemphasis(preemphasis),
-                streaming_cmvn(cmvn, bool(cmvn_running), num_coeffs))
-
-    def _setup(self, torch, computer, row_length: int, dtype, spec, coeff, cspec=None, cmvn_running=True):
-        """the device side: `computer`'s plan, the carry pool of ``2 * capacity * row_length`` samples, the
-        previous-sample pool (with a pre-emphasis), the staging buffers, the history pool of the deltas and the pool of
-        running sums of the cmvn"""
+        spec, coeff = streaming_deltas(deltas), streaming_preemphasis(preemphasis)
+        cspec = streaming_cmvn(cmvn, bool(cmvn_running), computer.num_coeffs)
+        self.state, row_length = self._new_state(computer, capacity)
+        # the device side: `computer`'s plan, the carry pool of ``2 * capacity * row_length`` samples, the
+        # previous-sample pool (with a pre-emphasis), the staging buffers, the history pool of the deltas and the pool
+        # of running sums of the cmvn
+        torch = _native.require_device()
         self._torch = torch
         self._lib = _native.lib()
         self.dtype = dtype
@@ -529,7 +620,7 @@ class _TickBatch:
         if any(a.ndim != 1 for a in arrs):
             raise ValueError("chunks must be 1-dimensional")
         lengths = np.fromiter(map(len, arrs), dtype=np.int64, count=len(arrs))
-        feats, rows = self._chunks_tick(ids, lengths, host_chunks=arrs)
+        feats, rows = self._tick(ids, lengths, host_chunks=arrs)
         return self._to_host(feats, rows, np.ones(len(ids), dtype=bool))
 
     def compute_chunks_packed(self, ids, d_samples, lengths) -> Tuple[object, np.ndarray]:
@@ -550,7 +641,7 @@ class _TickBatch:
             raise ValueError(f"d_samples must be a contiguous 1-D {self.dtype} or int16 tensor on {self.device}")
         if int(lengths.sum()) > d_samples.numel():
             raise ValueError("the chunks lie outside d_samples")
-        return self._chunks_tick(ids, lengths, d_samples=d_samples, i16=d_samples.dtype == torch.int16)
+        return self._tick(ids, lengths, d_samples=d_samples, i16=d_samples.dtype == torch.int16)
 
     def finalize(self, ids) -> List[np.ndarray]:
         """``finalize`` of streams `ids`: their last frames; the streams are reset and may be used again.  A stream
@@ -558,13 +649,13 @@ class _TickBatch:
         self._check_open()
         ids = self.state.check_ids(ids)
         started = self.state.started[ids].copy()
-        feats, rows = self._finalize_tick(ids)
+        feats, rows = self._tick(ids)
         return self._to_host(feats, rows, started)
 
     def finalize_packed(self, ids) -> Tuple[object, np.ndarray]:
         """:func:`finalize` with the features left on the GPU: ``(feats, rows)`` as :func:`compute_chunks_packed`"""
         self._check_open()
-        return self._finalize_tick(self.state.check_ids(ids))
+        return self._tick(self.state.check_ids(ids))
 
     def close(self) -> None:
         """Release the pools and the pinned buffers; the object cannot be used afterwards"""
@@ -600,14 +691,14 @@ class _TickBatch:
             buf = self._up[slot] = torch.empty(size, dtype=torch.int64, pin_memory=True)
         return slot, buf
 
-    def _send(self, slot: int, words: int):
-        """one copy of the first `words` of upload buffer `slot` to the device, on the current stream"""
+    def _send(self, slot: int, words: int, stream):
+        """one copy of the first `words` of upload buffer `slot` to the device, on `stream`"""
         torch = self._torch
         dev = torch.empty(max(words, 1), dtype=torch.int64, device=self.device)
         if words:
-            dev[:words].copy_(self._up[slot][:words], non_blocking=True)
+            dev.copy_(self._up[slot][:words], non_blocking=True)
             ev = self._up_events[slot] = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
+            ev.record(stream)
         return dev
 
     def _pack_chunks(self, host, host_chunks, lengths, total):
@@ -633,67 +724,120 @@ class _TickBatch:
             np.concatenate(host_chunks, out=host[:ns].view(self.dtype)[:total], casting="unsafe")
         return ns, i16
 
-    def _assemble_launch(self, samples, i16, d_meta, d_tile_prefix, n, tiles, work_len):
+    def _tick(self, ids, lengths=None, host_chunks=None, d_samples=None, i16=False):
+        """One tick over streams `ids`: ``compute_chunks`` of chunks of `lengths` -- `host_chunks`, or back to back in
+        `d_samples` on the device, of int16 if `i16` --, over the work buffer an assemble launch packs of every
+        stream's carry and chunk; without `lengths` ``finalize``, over the carries where they lie in the pool.  Returns
+        ``(feats, rows)``: the tick's rows on the device and every stream's first row in them"""
+        st = self.state
+        final = lengths is None
+        n = len(ids)
+        # every stream's span of samples: `span` of them from `off` of what the feature launch reads
+        if final:
+            step = st.finalize_step(ids)
+            span = step["carry_len"]
+            off = (step["half"] * self.capacity + ids) * self._row_length
+            total = ns = 0
+        else:
+            step = st.chunk_step(ids, lengths)
+            span = step["avail"]
+            work_off = _exclusive_cumsum(span)
+            off = work_off[:-1]
+            tile_prefix = _exclusive_cumsum((span + self._tile - 1) // self._tile)
+            total = int(lengths.sum())
+            ns = (total * self.dtype.itemsize + 7) // 8 if host_chunks is not None else 0
+        k = step["k"]
+        rows = _exclusive_cumsum(k)
+        row0 = rows[:-1]
+        order = self._emit_order(step, np.flatnonzero(k > 0))
+        up = _Upload(ns, _tick_layout(n, len(order), 4 + len(self._launch_extra), not final, self.dstate is not None,
+                                      self.cstate is not None))
+        slot, buf = self._staging(up.words)
+        up.pinned = buf.numpy()
+        if ns:
+            # (the staging was sized for samples of `dtype`; a tick that travels as int16 takes fewer words)
+            up.sample_words, i16 = self._pack_chunks(up.host("samples"), host_chunks, lengths, total)
+        if not final:
+            am = up.host("assemble")
+            am[:, 0] = ids
+            am[:, 1] = _exclusive_cumsum(lengths)[:-1]
+            am[:, 2] = lengths
+            am[:, 3] = step["carry_len"]
+            am[:, 4] = step.get("drop", 0)  # (a short-integration stream drops nothing of a chunk)
+            am[:, 5] = step["new_carry"]
+            am[:, 6] = off
+            am[:, 7] = step["word"]
+            up.host("tiles")[:] = tile_prefix
+        lm = up.host("launch")
+        lm[0], lm[1], lm[2], lm[3] = off[order], span[order], k[order], row0[order]
+        for r, key in enumerate(self._launch_extra, 4):
+            lm[r] = step[key][order]
+        if self.dstate is not None:
+            dstep = self.dstate.step(ids, k, final=final)
+            dstep["out_rows"] = _exclusive_cumsum(dstep["rows"])
+            elems = self.dstate.fill_meta(up.host("deltas"), up.host("elems"), ids, dstep, row0,
+                                          dstep["out_rows"][:-1], self._F)
+        if self.cstate is not None:
+            cstep = self.cstate.step(ids, k, final=final)
+            self.cstate.fill_meta(up.host("cmvn"), ids, cstep, row0)
+        stream = self._torch.cuda.current_stream(self.device)
+        up.device = self._send(slot, up.words, stream)
+        if final:
+            signal = self._pool.view(-1)
+        else:
+            samples = up.dev("samples") if host_chunks is not None else d_samples
+            signal = self._assemble_launch(samples if total else None, i16, up.dev("assemble"), up.dev("tiles"), n,
+                                           int(tile_prefix[-1]), int(work_off[-1]), stream)
+        feats = self._feature_launch(signal, up.dev("launch"), order, step, off, span, rows, stream)
+        if final:
+            st.reset(ids)
+        else:
+            st.commit_chunks(ids, step)
+        if self.cstate is not None:
+            self._cmvn_launch(feats, up.dev("cmvn"), ids, cstep, stream)
+        if self.dstate is not None:
+            return self._delta_launch(feats, up.dev("deltas"), up.dev("elems"), ids, dstep, elems, stream)
+        return feats, rows
+
+    def _assemble_launch(self, samples, i16, d_meta, d_tile_prefix, n, tiles, work_len, stream):
         """one pds_multistream_assemble launch: the tick's work buffer (returned) and the new carries, in the other
         pool half; `samples`: the device tensor the chunks start in (only its address is used; None: no samples)"""
         torch = self._torch
         work = torch.empty(max(work_len, 1), dtype=self._tdtype, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
         chunks = samples.data_ptr() if samples is not None else None
         if i16 or self._prev is not None:
             rc = self._lib.pds_multistream_assemble_pcm(
                 _SAMPLES_I16 if i16 else self._format, self._format, chunks, self._pool.data_ptr(), self.capacity,
                 self._row_length, d_meta.data_ptr(), d_tile_prefix.data_ptr(), n, tiles, work.data_ptr(),
-                self.preemphasis, self._prev.data_ptr() if self._prev is not None else None, stream)
+                self.preemphasis, self._prev.data_ptr() if self._prev is not None else None, stream.cuda_stream)
         else:
             rc = self._assemble(chunks, self._pool.data_ptr(), self.capacity, self._row_length, d_meta.data_ptr(),
-                                d_tile_prefix.data_ptr(), n, tiles, work.data_ptr(), stream)
+                                d_tile_prefix.data_ptr(), n, tiles, work.data_ptr(), stream.cuda_stream)
         _native.check(rc, "pds_multistream_assemble")
         return work
 
-    def _delta_meta(self, words, ids, k, static_rows, final):
-        """the deltas part of a tick's upload into `words` (pinned int64): the streams' step, the number of elements"""
-        n = len(ids)
-        dstep = self.dstate.step(ids, k, final=final)
-        dstep["out_rows"] = _exclusive_cumsum(dstep["rows"])
-        elems = self.dstate.fill_meta(words[: _DFIELDS * n].reshape(n, _DFIELDS), words[_DFIELDS * n :], ids, dstep,
-                                      static_rows, dstep["out_rows"][:-1], self._F)
-        return dstep, elems
-
-    def _delta_launch(self, statics, d_words, ids, dstep, elems):
-        """one pds_multistream_deltas launch over the tick's `statics`: the rows due and the next histories"""
-        torch = self._torch
-        n = len(ids)
-        rows = dstep["out_rows"]
-        out = torch.empty((int(rows[-1]), self.num_coeffs), dtype=self._tdtype, device=self.device)
-        rc = self._deltas_fn(statics.data_ptr() if statics.shape[0] else None, self._hist.data_ptr(), self.capacity,
-                             self.dstate.hist_rows, self._F, self._d_filts.data_ptr(), self._d_filt_off.data_ptr(),
-                             self._K, d_words.data_ptr(), d_words[_DFIELDS * n :].data_ptr(), n, elems,
-                             out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-        _native.check(rc, "pds_multistream_deltas")
-        self.dstate.commit(ids, dstep)
-        return out, rows
-
-    def _cmvn_words(self, n: int) -> int:
-        """int64 words of the cmvn part of a tick's upload (0 without cmvn)"""
-        return _CFIELDS * n if self.cstate is not None else 0
-
-    def _cmvn_meta(self, words, ids, k, static_rows, final):
-        """the cmvn part of a tick's upload into `words` (pinned int64): the streams' step"""
-        cstep = self.cstate.step(ids, k, final=final)
-        self.cstate.fill_meta(words.reshape(len(ids), _CFIELDS), ids, cstep, static_rows)
-        return cstep
-
-    def _cmvn_launch(self, statics, d_words, ids, cstep):
+    def _cmvn_launch(self, statics, d_meta, ids, cstep, stream):
         """one pds_multistream_cmvn launch, in place over the tick's `statics` (none in a tick without new rows: no
         stream's sums change then)"""
         if statics.shape[0]:
             rc = self._cmvn_fn(statics.data_ptr(), self._sums.data_ptr() if self._sums is not None else None,
                                self.capacity, self._F, self._d_prior.data_ptr() if self._d_prior is not None else None,
-                               int(self._norm_var), int(self.cstate.running), d_words.data_ptr(), len(ids),
-                               self._torch.cuda.current_stream(self.device).cuda_stream)
+                               int(self._norm_var), int(self.cstate.running), d_meta.data_ptr(), len(ids),
+                               stream.cuda_stream)
             _native.check(rc, "pds_multistream_cmvn")
         self.cstate.commit(ids, cstep)
+
+    def _delta_launch(self, statics, d_meta, d_elem_prefix, ids, dstep, elems, stream):
+        """one pds_multistream_deltas launch over the tick's `statics`: the rows due and the next histories"""
+        rows = dstep["out_rows"]
+        out = self._torch.empty((int(rows[-1]), self.num_coeffs), dtype=self._tdtype, device=self.device)
+        rc = self._deltas_fn(statics.data_ptr() if statics.shape[0] else None, self._hist.data_ptr(), self.capacity,
+                             self.dstate.hist_rows, self._F, self._d_filts.data_ptr(), self._d_filt_off.data_ptr(),
+                             self._K, d_meta.data_ptr(), d_elem_prefix.data_ptr(), len(ids), elems, out.data_ptr(),
+                             stream.cuda_stream)
+        _native.check(rc, "pds_multistream_deltas")
+        self.dstate.commit(ids, dstep)
+        return out, rows
 
     def _to_host(self, feats, rows, started) -> List[np.ndarray]:
         """one download into pinned memory, one synchronisation, views per stream"""
@@ -755,120 +899,37 @@ class StreamBatch(_TickBatch):
     the computer's path, not bit for bit); a `cmvn` then works on the widened features.
     """
 
-    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None, cmvn=None,
-                 cmvn_running=True):
-        if not isinstance(computer, ShortTimeFourierTransformFrameComputer):
-            raise TypeError("StreamBatch serves STFT frame computers (streaming short integration is not supported "
-                            "here: multistream_si.SiStreamBatch serves those)")
-        dtype, spec, coeff, cspec = self._check_args(dtype, deltas, preemphasis, cmvn, cmvn_running,
-                                                     computer.num_coeffs)
-        torch = _native.require_device()
-        self.state = StreamState(capacity, computer.frame_length, computer.frame_shift, computer.pad_left)
-        self._setup(torch, computer, computer.frame_length, dtype, spec, coeff, cspec, cmvn_running)
+    _computer_type = ShortTimeFourierTransformFrameComputer
+    _wrong_computer = ("StreamBatch serves STFT frame computers (streaming short integration is not supported here: "
+                       "multistream_si.SiStreamBatch serves those)")
 
-    # ---- a tick ---------------------------------------------------------------------
+    @staticmethod
+    def _new_state(computer, capacity):
+        return (StreamState(capacity, computer.frame_length, computer.frame_shift, computer.pad_left),
+                computer.frame_length)
 
-    def _launch_groups(self, signal, d_lm, order, cp, k, offsets, lengths, row_off, R):
-        """the STFT batch launches of one tick: streams `order` (sorted by carry pad), one launch per distinct pad;
-        `d_lm` is the device int64[4, len(order)] of their offsets, lengths, frame counts and rows"""
+    @staticmethod
+    def _emit_order(step, emit):
+        """sorted by carry pad: the left reflection is launch-wide"""
+        return emit[np.argsort(step["cp"][emit], kind="stable")]
+
+    def _feature_launch(self, signal, d_lm, order, step, off, span, rows, stream):
+        """the STFT batch launches of one tick (on the current stream, as the computer launches): streams `order`, one
+        launch per distinct carry pad; `d_lm` is the device int64[4, len(order)] of their offsets, lengths, frame
+        counts and rows"""
         torch = self._torch
-        C = self._F
+        k, cp, R = step["k"], step["cp"], int(rows[-1])
         f32_arith = self.dtype == np.float64 and config.FLOAT64_ARITHMETIC == "float32"
         if f32_arith:
             signal = signal.to(torch.float32)
-        feats = torch.empty((R, C), dtype=torch.float32 if f32_arith else self._tdtype, device=self.device)
+        feats = torch.empty((R, self._F), dtype=torch.float32 if f32_arith else self._tdtype, device=self.device)
         if len(order):
             pads = cp[order]
-            cuts = np.flatnonzero(np.diff(pads)) + 1
-            for lo, hi in zip(np.concatenate([[0], cuts]), np.concatenate([cuts, [len(order)]])):
+            cuts = [0, *(np.flatnonzero(np.diff(pads)) + 1).tolist(), len(order)]
+            for lo, hi in zip(cuts[:-1], cuts[1:]):
                 sel = order[lo:hi]
                 # (rows go to the tick's order through d_meta[3]; host row_offsets only bound the output)
-                layout = PackedLayout(B=int(hi - lo), extent=int((offsets[sel] + lengths[sel]).max()),
-                                      nframes=k[sel], row_offsets=np.append(row_off[sel], R), d_meta=d_lm[:, lo:hi])
+                layout = PackedLayout(B=hi - lo, extent=int((off[sel] + span[sel]).max()),
+                                      nframes=k[sel], row_offsets=np.append(rows[:-1][sel], R), d_meta=d_lm[:, lo:hi])
                 self._comp.launch(signal, layout, out=feats, pad_left=int(pads[lo]))
         return feats.to(self._tdtype) if f32_arith else feats
-
-    def _chunks_tick(self, ids, lengths, host_chunks=None, d_samples=None, i16=False):
-        torch = self._torch
-        st = self.state
-        step = st.chunk_step(ids, lengths)
-        n = len(ids)
-        avail, k, cp = step["avail"], step["k"], step["cp"]
-        work_off = _exclusive_cumsum(avail)
-        rows = _exclusive_cumsum(k)
-        R = int(rows[-1])
-        tile_prefix = _exclusive_cumsum((avail + self._tile - 1) // self._tile)
-        emit = np.flatnonzero(k > 0)
-        order = emit[np.argsort(cp[emit], kind="stable")]
-        E = len(order)
-        # upload: [samples][assemble metadata n x 8][tile prefix n + 1][launch metadata 4 x E], int64 words, and with
-        # deltas [deltas metadata n x 8][element prefix n + 1], with cmvn [cmvn metadata n x 8] behind them
-        total = int(lengths.sum())
-        ns = (total * self.dtype.itemsize + 7) // 8 if host_chunks is not None else 0
-        rest = _FIELDS * n + (n + 1) + 4 * E
-        dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
-        cwords = self._cmvn_words(n)
-        slot, buf = self._staging(ns + rest + dwords + cwords)
-        host = buf.numpy()
-        if ns:
-            ns, i16 = self._pack_chunks(host, host_chunks, lengths, total)
-        words = ns + rest
-        if dwords:
-            dstep, elems = self._delta_meta(host[words : words + dwords], ids, k, rows[:-1], final=False)
-        if cwords:
-            cstep = self._cmvn_meta(host[words + dwords : words + dwords + cwords], ids, k, rows[:-1], final=False)
-        am = host[ns : ns + _FIELDS * n].reshape(n, _FIELDS)
-        am[:, 0] = ids
-        am[:, 1] = _exclusive_cumsum(lengths)[:-1]
-        am[:, 2] = lengths
-        am[:, 3] = step["carry_len"]
-        am[:, 4] = step["drop"]
-        am[:, 5] = step["new_carry"]
-        am[:, 6] = work_off[:-1]
-        am[:, 7] = step["word"]
-        at = ns + _FIELDS * n
-        host[at : at + n + 1] = tile_prefix
-        lm = host[at + n + 1 : words].reshape(4, E)
-        lm[0], lm[1], lm[2], lm[3] = work_off[:-1][order], avail[order], k[order], rows[:-1][order]
-        dev = self._send(slot, words + dwords + cwords)
-        samples = dev[:ns] if host_chunks is not None else d_samples  # (only its address is used)
-        work = self._assemble_launch(samples if total else None, i16, dev[ns:], dev[at:], n, int(tile_prefix[-1]),
-                                     int(work_off[-1]))
-        feats = self._launch_groups(work, dev[at + n + 1 : words].view(4, E), order, cp, k, work_off[:-1], avail,
-                                    rows[:-1], R)
-        st.commit_chunks(ids, step)
-        if cwords:
-            self._cmvn_launch(feats, dev[words + dwords :], ids, cstep)
-        if dwords:
-            return self._delta_launch(feats, dev[words : words + dwords], ids, dstep, elems)
-        return feats, rows
-
-    def _finalize_tick(self, ids):
-        st = self.state
-        step = st.finalize_step(ids)
-        c, cp, k = step["carry_len"], step["cp"], step["k"]
-        rows = _exclusive_cumsum(k)
-        R = int(rows[-1])
-        offsets = (step["half"] * self.capacity + ids) * st.L  # the carries where they lie in the pool
-        emit = np.flatnonzero(k > 0)
-        order = emit[np.argsort(cp[emit], kind="stable")]
-        E = len(order)
-        n = len(ids)
-        dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
-        cwords = self._cmvn_words(n)
-        slot, buf = self._staging(4 * E + dwords + cwords)
-        lm = buf.numpy()[: 4 * E].reshape(4, E)
-        lm[0], lm[1], lm[2], lm[3] = offsets[order], c[order], k[order], rows[:-1][order]
-        if dwords:
-            dstep, elems = self._delta_meta(buf.numpy()[4 * E : 4 * E + dwords], ids, k, rows[:-1], final=True)
-        if cwords:
-            cstep = self._cmvn_meta(buf.numpy()[4 * E + dwords : 4 * E + dwords + cwords], ids, k, rows[:-1], final=True)
-        dev = self._send(slot, 4 * E + dwords + cwords)
-        feats = self._launch_groups(self._pool.view(-1), dev[: 4 * E].view(4, E), order, cp, k, offsets, c,
-                                    rows[:-1], R)
-        st.reset(ids)
-        if cwords:
-            self._cmvn_launch(feats, dev[4 * E + dwords :], ids, cstep)
-        if dwords:
-            return self._delta_launch(feats, dev[4 * E : 4 * E + dwords], ids, dstep, elems)
-        return feats, rows

@@ -37,7 +37,9 @@ in one copy from pinned memory; one ``pds_multistream_assemble_*`` launch writes
 the frames of every stream that has any, each continued at its own `start` (float32: the plan's overlap-save form
 when it has one, else direct filtering; float64: direct filtering -- the choices the single-stream computer makes);
 optionally one ``pds_multistream_cmvn_*`` launch and one ``pds_multistream_deltas_*`` launch, in that order; one
-download.  ``finalize`` reads the carries where they lie in the pool.
+download.  ``finalize`` reads the carries where they lie in the pool.  The pipeline is :func:`multistream._TickBatch._tick`,
+shared with ``StreamBatch``; this module adds the state, the tick order of the emitting streams, the `start` row of the
+launch metadata and the ``pds_si_batch_starts_*`` call.
 
 The per-utterance start is what makes one call enough.  A stream's `start` is ``skip0 - lead + done * S - tail_at``:
 the position of its next frame's first integrated sample, relative to the first sample it still keeps.  Once
@@ -54,19 +56,17 @@ and the tail is everything: ``P < skip0`` under a pending skip, else ``P < skip0
 
 Not thread-safe; works on the current torch stream of the device that was current at construction.
 """
-from typing import Tuple
-
 import numpy as np
 
 from . import _native
 from .compute import _MAX_UTTS_PER_CALL
-from .multistream import _DFIELDS, _FIELDS, _HAS_SAMPLE, StreamState, _exclusive_cumsum, _TickBatch
+from .multistream import _StreamWords, _TickBatch
 from .si import ShortIntegrationFrameComputer
 
 __all__ = ["SiStreamBatch", "SiStreamState"]
 
 
-class SiStreamState:
+class SiStreamState(_StreamWords):
     """Host bookkeeping of many short-integration streams: ``si.py``'s ``_reset_stream`` / ``compute_chunk`` / ``_emit``
     / ``finalize`` applied to arrays of streams.  Needs no device.
 
@@ -75,16 +75,13 @@ class SiStreamState:
 
     Per stream: ``done`` frames emitted, ``waiting`` integrated samples received but not yet framed, ``skip_left`` of the
     skip still pending, ``tail_at`` stream position of the first kept sample, ``carry_len`` kept samples (always
-    < :attr:`row_length`), ``started`` between the first chunk and ``finalize``, and the pool half / has-sample ``word``
-    laid out as in :class:`multistream.StreamState`.
+    < :attr:`row_length`), and ``started``, ``has_sample`` and ``half`` as :class:`multistream.StreamState` has them.
     """
 
     def __init__(self, capacity: int, frame_shift: int, max_support: int, translation: int, skip0: int, lead: int,
                  centered: bool):
-        capacity = int(capacity)
-        if capacity <= 0:
-            raise ValueError("capacity must be positive")
-        self.capacity = capacity
+        super().__init__(capacity)
+        capacity = self.capacity
         self.S, self.M, self.translation = int(frame_shift), int(max_support), int(translation)
         self.skip0, self.lead, self.centered = int(skip0), int(lead), bool(centered)
         if self.S < 1 or self.M < 1 or self.skip0 < 0 or self.lead < 0 or (self.skip0 and self.lead):
@@ -97,18 +94,12 @@ class SiStreamState:
         self.skip_left = np.zeros(capacity, dtype=np.int64)
         self.tail_at = np.zeros(capacity, dtype=np.int64)
         self.carry_len = np.zeros(capacity, dtype=np.int64)
-        self.started = np.zeros(capacity, dtype=bool)
-        self.word = np.zeros(capacity, dtype=np.int64)
 
     @classmethod
     def of(cls, computer: ShortIntegrationFrameComputer, capacity: int) -> "SiStreamState":
         """the state of `capacity` streams of `computer`"""
         return cls(capacity, computer.frame_shift, computer._max_support, computer._translation, computer._skip0,
                    computer._lead, computer.frame_style == "centered")
-
-    half = StreamState.half
-    has_sample = StreamState.has_sample
-    check_ids = StreamState.check_ids
 
     def _start(self, done, tail_at):
         """the kernel's `start` for a span that begins at stream position `tail_at`, continued at frame `done`"""
@@ -140,7 +131,7 @@ class SiStreamState:
             carry_len=c, avail=avail, k=k, start=self._start(done, tail_at), new_carry=new_carry,
             next_done=next_done, next_waiting=waiting - k * S, next_skip_left=skip_left, next_tail_at=keep_from,
             next_carry_len=avail - new_carry,
-            word=word, next_word=(word ^ 1) | (lengths > 0) * _HAS_SAMPLE,
+            word=word, next_word=self.next_word(word, lengths),
         )
         assert (new_carry >= 0).all() and (new_carry <= avail).all()
         assert (step["next_carry_len"] < self.row_length).all()
@@ -197,122 +188,44 @@ class SiStreamBatch(_TickBatch):
     scratch (``pds_si_scratch_len`` of the tick's streams and its largest frame count).
     """
 
-    def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None, cmvn=None,
-                 cmvn_running=True):
-        if not isinstance(computer, ShortIntegrationFrameComputer):
-            raise TypeError("SiStreamBatch serves short-integration frame computers (multistream.StreamBatch serves "
-                            "STFT ones)")
-        dtype, spec, coeff, cspec = self._check_args(dtype, deltas, preemphasis, cmvn, cmvn_running,
-                                                     computer.num_coeffs)
-        torch = _native.require_device()
-        self.state = SiStreamState.of(computer, capacity)
-        self._setup(torch, computer, self.state.row_length, dtype, spec, coeff, cspec, cmvn_running)
-        self._batch = self._lib.pds_si_batch_starts_f32 if dtype == np.float32 else self._lib.pds_si_batch_starts_f64
+    _computer_type = ShortIntegrationFrameComputer
+    _wrong_computer = ("SiStreamBatch serves short-integration frame computers (multistream.StreamBatch serves STFT "
+                       "ones)")
+    _launch_extra = ("start",)
 
-    # ---- a tick ---------------------------------------------------------------------
+    @staticmethod
+    def _new_state(computer, capacity):
+        state = SiStreamState.of(computer, capacity)
+        return state, state.row_length
 
-    def _si_launch(self, signal, d_lm, k, R):
-        """the frames of a tick: one pds_si_batch_starts call over the streams of `d_lm`, the device int64[5, E] of their
-        offsets in `signal`, lengths, frame counts `k` (host copy), first rows and starts; more than one call only
-        beyond the utterances a call takes"""
+    @staticmethod
+    def _emit_order(step, emit):
+        return emit  # (tick order: every stream brings its own start)
+
+    def _feature_launch(self, signal, d_lm, order, step, off, span, rows, stream):
+        """the frames of a tick: one pds_si_batch_starts call over streams `order`; `d_lm` is the device
+        int64[5, len(order)] of their offsets in `signal`, lengths, frame counts, first rows and starts; more than one
+        call only beyond the utterances a call takes"""
         torch = self._torch
         lib = self._lib
-        feats = torch.empty((R, self._F), dtype=self._tdtype, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        f64 = self.dtype == np.float64
+        batch = lib.pds_si_batch_starts_f64 if f64 else lib.pds_si_batch_starts_f32
+        feats = torch.empty((int(rows[-1]), self._F), dtype=self._tdtype, device=self.device)
+        k = step["k"][order]
         E = len(k)
         for lo in range(0, E, _MAX_UTTS_PER_CALL):
             hi = min(E, lo + _MAX_UTTS_PER_CALL)
             most = int(k[lo:hi].max())
-            args = (self._plan.handle, signal.data_ptr()) + tuple(d_lm[r, lo:].data_ptr() for r in range(5)) + (
-                hi - lo, most)
-            if self.dtype == np.float64:
-                rc = self._batch(*args, feats.data_ptr(), feats.stride(0), stream)
+            at, row = d_lm.data_ptr() + 8 * lo, 8 * d_lm.stride(0)  # (int64[5, E], a row per argument)
+            args = (self._plan.handle, signal.data_ptr()) + tuple(at + r * row for r in range(5)) + (hi - lo, most)
+            if f64:
+                rc = batch(*args, feats.data_ptr(), feats.stride(0), stream.cuda_stream)
             else:
                 # the overlap-save form when the plan has it (it needs scratch memory), else direct filtering: the
                 # choice of ShortIntegrationFrameComputer._launch
                 need = int(lib.pds_si_scratch_len(self._plan.handle, hi - lo, most))
                 scratch = torch.empty(need, dtype=torch.float32, device=self.device) if need else None
-                rc = self._batch(*args, scratch.data_ptr() if need else None, feats.data_ptr(), feats.stride(0),
-                                 stream)
+                rc = batch(*args, scratch.data_ptr() if need else None, feats.data_ptr(), feats.stride(0),
+                           stream.cuda_stream)
             _native.check(rc, "pds_si_batch_starts")
         return feats
-
-    def _chunks_tick(self, ids, lengths, host_chunks=None, d_samples=None, i16=False):
-        st = self.state
-        step = st.chunk_step(ids, lengths)
-        n = len(ids)
-        avail, k = step["avail"], step["k"]
-        work_off = _exclusive_cumsum(avail)
-        rows = _exclusive_cumsum(k)
-        R = int(rows[-1])
-        tile_prefix = _exclusive_cumsum((avail + self._tile - 1) // self._tile)
-        emit = np.flatnonzero(k > 0)
-        E = len(emit)
-        # upload: [samples][assemble metadata n x 8][tile prefix n + 1][launch metadata 5 x E], int64 words, and with
-        # deltas [deltas metadata n x 8][element prefix n + 1], with cmvn [cmvn metadata n x 8] behind them
-        total = int(lengths.sum())
-        ns = (total * self.dtype.itemsize + 7) // 8 if host_chunks is not None else 0
-        rest = _FIELDS * n + (n + 1) + 5 * E
-        dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
-        cwords = self._cmvn_words(n)
-        slot, buf = self._staging(ns + rest + dwords + cwords)
-        host = buf.numpy()
-        if ns:
-            ns, i16 = self._pack_chunks(host, host_chunks, lengths, total)
-        words = ns + rest
-        if dwords:
-            dstep, elems = self._delta_meta(host[words : words + dwords], ids, k, rows[:-1], final=False)
-        if cwords:
-            cstep = self._cmvn_meta(host[words + dwords : words + dwords + cwords], ids, k, rows[:-1], final=False)
-        am = host[ns : ns + _FIELDS * n].reshape(n, _FIELDS)
-        am[:, 0] = ids
-        am[:, 1] = _exclusive_cumsum(lengths)[:-1]
-        am[:, 2] = lengths
-        am[:, 3] = step["carry_len"]
-        am[:, 4] = 0  # (nothing of a chunk is dropped)
-        am[:, 5] = step["new_carry"]
-        am[:, 6] = work_off[:-1]
-        am[:, 7] = step["word"]
-        at = ns + _FIELDS * n
-        host[at : at + n + 1] = tile_prefix
-        lm = host[at + n + 1 : words].reshape(5, E)
-        lm[0], lm[1], lm[2], lm[3], lm[4] = work_off[:-1][emit], avail[emit], k[emit], rows[:-1][emit], step["start"][emit]
-        dev = self._send(slot, words + dwords + cwords)
-        samples = dev[:ns] if host_chunks is not None else d_samples  # (only its address is used)
-        work = self._assemble_launch(samples if total else None, i16, dev[ns:], dev[at:], n, int(tile_prefix[-1]),
-                                     int(work_off[-1]))
-        feats = self._si_launch(work, dev[at + n + 1 : words].view(5, E), k[emit], R)
-        st.commit_chunks(ids, step)
-        if cwords:
-            self._cmvn_launch(feats, dev[words + dwords :], ids, cstep)
-        if dwords:
-            return self._delta_launch(feats, dev[words : words + dwords], ids, dstep, elems)
-        return feats, rows
-
-    def _finalize_tick(self, ids) -> Tuple[object, np.ndarray]:
-        st = self.state
-        step = st.finalize_step(ids)
-        c, k = step["carry_len"], step["k"]
-        rows = _exclusive_cumsum(k)
-        R = int(rows[-1])
-        offsets = (step["half"] * self.capacity + ids) * self._row_length  # the carries where they lie in the pool
-        emit = np.flatnonzero(k > 0)
-        E = len(emit)
-        n = len(ids)
-        dwords = _DFIELDS * n + (n + 1) if self.dstate is not None else 0
-        cwords = self._cmvn_words(n)
-        slot, buf = self._staging(5 * E + dwords + cwords)
-        lm = buf.numpy()[: 5 * E].reshape(5, E)
-        lm[0], lm[1], lm[2], lm[3], lm[4] = offsets[emit], c[emit], k[emit], rows[:-1][emit], step["start"][emit]
-        if dwords:
-            dstep, elems = self._delta_meta(buf.numpy()[5 * E : 5 * E + dwords], ids, k, rows[:-1], final=True)
-        if cwords:
-            cstep = self._cmvn_meta(buf.numpy()[5 * E + dwords : 5 * E + dwords + cwords], ids, k, rows[:-1], final=True)
-        dev = self._send(slot, 5 * E + dwords + cwords)
-        feats = self._si_launch(self._pool.view(-1), dev[: 5 * E].view(5, E), k[emit], R)
-        st.reset(ids)
-        if cwords:
-            self._cmvn_launch(feats, dev[5 * E + dwords :], ids, cstep)
-        if dwords:
-            return self._delta_launch(feats, dev[5 * E : 5 * E + dwords], ids, dstep, elems)
-        return feats, rows
