@@ -95,6 +95,10 @@ int32_t pds_stft_plan_kernel_kind(const pds_stft_plan *plan);
  * format), and in bits 8-11 which of the four the plan built tables for (bit 8 + id).  -1: no fused kernel.  The
  * environment's PDS_STFT_WALK = ell | seg | rseg | mseg, read when the plan is created, forces a walk that was built */
 int32_t pds_stft_plan_filter_walk(const pds_stft_plan *plan);
+/* the instantiation of the fused kernel a launch of the plan dispatches to: out = (N1, N2, ROWS) = in-lane transform
+ * size, lanes per frame and the row count the instantiation is built for (the smallest one of that transform size
+ * with ROWS >= ceil(frame_length / N2)); zeros for a plan on the generic kernels */
+int32_t pds_stft_plan_geometry(const pds_stft_plan *plan, int32_t out[3]);
 
 /*
  * Batched compute_full (compute.py:574-607) over B utterances packed in one buffer.

@@ -100,6 +100,7 @@ SIGNATURES = {
     "pds_stft_num_frames": (c_int64, [c_void_p, c_int64]),
     "pds_stft_plan_kernel_kind": (c_int32, [c_void_p]),
     "pds_stft_plan_filter_walk": (c_int32, [c_void_p]),
+    "pds_stft_plan_geometry": (c_int32, [c_void_p, POINTER(c_int32)]),
     "pds_stft_batch_f32": (c_int32, _BATCH_ARGS),
     "pds_stft_batch_f64": (c_int32, _BATCH_ARGS),
     "pds_stft_batch_f32_generic": (c_int32, _BATCH_ARGS),

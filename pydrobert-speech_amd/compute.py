@@ -227,6 +227,10 @@ class _NativePlan:
         walks, bits = ("ell", "seg", "rseg", "mseg"), lib.pds_stft_plan_filter_walk(handle)
         self.walk = walks[bits & 255] if bits >= 0 else None
         self.walks_built = tuple(w for i, w in enumerate(walks) if bits >= 0 and bits >> (8 + i) & 1)
+        # (n1, n2, rows) of the stft_geoms.def line a launch dispatches to ((0, 0, 0): no fused kernel)
+        geometry = (ctypes.c_int32 * 3)()
+        _native.check(lib.pds_stft_plan_geometry(handle, geometry), "pds_stft_plan_geometry")
+        self.geometry = tuple(int(v) for v in geometry)
         self.has_f64in = bool(lib.pds_stft_plan_has_f64in(handle))
         self.has_i16in = bool(lib.pds_stft_plan_has_i16in(handle))
         self.has_fused_deltas = bool(lib.pds_stft_plan_has_fused_deltas(handle))

@@ -131,6 +131,13 @@ int64_t pds_stft_num_frames(const pds_stft_plan *p, int64_t n) {
 }
 
 int32_t pds_stft_plan_kernel_kind(const pds_stft_plan *p) { return p ? p->fast.kind : 0; }
+int32_t pds_stft_plan_geometry(const pds_stft_plan *p, int32_t out[3]) {
+  if (!out) return PDS_ERR_INVALID;
+  out[0] = out[1] = out[2] = 0;
+  if (!p) return PDS_ERR_INVALID;
+  pds::fast_plan_geometry(p, out);
+  return PDS_OK;
+}
 int32_t pds_stft_plan_filter_walk(const pds_stft_plan *p) {
   if (!p || !p->fast.kind) return -1;
   const auto &ft = p->fast;

@@ -152,6 +152,8 @@ int32_t fast_tables_create(pds_stft_plan *plan, const double *window, const int3
                            const int32_t *col, const double *val);
 void fast_tables_destroy(pds_stft_plan *plan);
 int32_t launch_stft_fast_f32(const pds_stft_plan *plan, const BatchArgs &a);
+// out = (N1, N2, ROWS) of the stft_geoms.def line the launch dispatches to, zeros without a fused kernel
+void fast_plan_geometry(const pds_stft_plan *plan, int32_t out[3]);
 bool fast_has_f64in(const pds_stft_plan *plan);
 bool fast_has_fused_deltas(const pds_stft_plan *plan);
 bool fast_has_fused_cmvn(const pds_stft_plan *plan);

@@ -18,10 +18,16 @@ bool fast_has_f64in(const pds_stft_plan *plan) { return plan->fast.kind && fast_
 
 // (fused CMVN sums: the 16-lane power-of-two geometries with a segment walk; whether the waves' sums fit in LDS
 // beside the walk's tables is decided at the launch, which refuses otherwise)
+static int fast_geometry_rows(const FastTables &ft, int *minw);
+
 bool fast_has_fused_cmvn(const pds_stft_plan *plan) {
   const FastTables &ft = plan->fast;
-  // (the 128-register row-segment kernel of N = 512 does without: see STATS in the kernel)
-  return ft.kind && ft.n2 == 16 && ((ft.n1 == 64 && ft.walk != 0) || (ft.n1 == 32 && (ft.walk == 1 || ft.walk == 3)));
+  // (the row-segment kernels take the sums at two waves per SIMD only -- STATS in the kernel -- and every 16-lane
+  // power-of-two line of stft_geoms.def asks for three or four: a plan on that walk said yes here, and the launch
+  // then declined every call)
+  int minw = 0;
+  if (!ft.kind || ft.n2 != 16 || (ft.n1 != 32 && ft.n1 != 64) || !fast_geometry_rows(ft, &minw)) return false;
+  return ft.walk == 1 || ft.walk == 3 || (ft.walk == 2 && minw <= 2);
 }
 
 bool fast_has_fused_deltas(const pds_stft_plan *plan) {
@@ -68,12 +74,39 @@ PDS_GEOM(32, 16, 25, 4)
 #endif
 #undef PDS_GEOM
 
+// ROWS of the instantiation that serves the plan: the smallest row count of its (N1, N2) that holds the frame, in
+// the order of stft_geoms.def; 0: none.  The dispatch below, pds_stft_plan_geometry and fast_has_fused_cmvn all ask
+// here.  `minw`, if given: the waves per SIMD of that instantiation's launch bounds.
+static int fast_geometry_rows(const FastTables &ft, int *minw = nullptr) {
+  if (!ft.kind) return 0;
+#define PDS_GEOM(N1, N2, R, MINW)                          \
+  if (ft.n1 == N1 && ft.n2 == N2 && ft.rows <= R) {        \
+    if (minw) *minw = MINW;                                \
+    return R;                                              \
+  }
+#ifdef PDS_DEV_ONLY512  // (ISA inspection and variant builds: the headline geometry alone)
+  PDS_GEOM(32, 16, 25, 4)
+#else
+#include "stft_geoms.def"
+#endif
+#undef PDS_GEOM
+  return 0;
+}
+
+void fast_plan_geometry(const pds_stft_plan *plan, int32_t out[3]) {
+  const FastTables &ft = plan->fast;
+  const int rows = fast_geometry_rows(ft);
+  out[0] = rows ? ft.n1 : 0;
+  out[1] = rows ? ft.n2 : 0;
+  out[2] = rows;
+}
+
 int32_t launch_stft_fast_f32(const pds_stft_plan *plan, const BatchArgs &a) {
   const FastTables &ft = plan->fast;
-  // the smallest row count of the plan's (N1, N2) that holds the frame
+  const int rows = fast_geometry_rows(ft);
 #define PDS_GEOM(N1, N2, R, MINW) \
-  if (ft.n1 == N1 && ft.n2 == N2 && ft.rows <= R) return launch_geom_##N1##_##N2##_##R(plan, a);
-#ifdef PDS_DEV_ONLY512  // (ISA inspection and variant builds: the headline geometry alone)
+  if (ft.n1 == N1 && ft.n2 == N2 && rows == R) return launch_geom_##N1##_##N2##_##R(plan, a);
+#ifdef PDS_DEV_ONLY512
   PDS_GEOM(32, 16, 25, 4)
 #else
 #include "stft_geoms.def"

@@ -191,7 +191,17 @@ int32_t launch_wave(const pds_stft_plan *plan, const BatchArgs &a) {
     set_error("stft_batch_i16in: not served for this plan (filter table outside LDS)");
     return PDS_ERR_INVALID;
   }
-  if (pre && !in_lds) return launch_stft_generic_f32(plan, a);
+  if (pre && !in_lds) {
+    // (the direct-DFT kernel reads float32 samples and stores float32 statics, nothing else: handed float64 samples
+    // it read their halves as floats and returned PDS_OK -- pds_stft_batch_f64in with a pre-emphasis on an N = 2048
+    // gammatone bank -- and a statics + deltas or CMVN call would have got its statics alone)
+    if (a.in_f64 || a.out_f64 || a.dl_K > 0 || a.d_stat_part) {
+      set_error("stft_batch: fused pre-emphasis with the filter table outside LDS is served for float32 samples and plain "
+                "float32 features only");
+      return PDS_ERR_INVALID;
+    }
+    return launch_stft_generic_f32(plan, a);
+  }
   p.preemph = (float)a.preemph;
   p.preemph_d = a.preemph;
   p.waves = waves;

@@ -39,12 +39,13 @@ EPS64 = 2.0 ** -53
 FULL_SCALE = 32767.0
 
 # Worst kappa the float32 restatements below need, measured by calibrate() on the CPU (numpy 2.2.6, whose float32
-# rFFT keeps complex64) over suite_configs() -- the five fixture configurations, the 17 EXTRA_GEOMETRIES of
+# rFFT keeps complex64) over suite_configs() -- the five fixture configurations, the 25 EXTRA_GEOMETRIES of
 # test_gpu_stft.py and the N = 8192 configuration -- and every family and level of cases(), as float32 samples and
 # as int16-quantised ones.  test_structured_model.py::test_calibration recomputes both and fails if either grows.
 # Never derived from what a kernel produces.
 #   FFT form: 0.290 (chirp, N = 8192); 0.283 chirp n4096_fbank_48k; 0.271 quantised chirp n1024_full_rows; the chirp
-#   is the worst family of 19 of the 23 configurations.  (With a float32 pre-emphasis in front: 0.46, chirp, N = 4096.)
+#   is the worst family of 19 of the first 23 configurations; the eight row-bucket ones added since need 0.06 - 0.253
+#   (direct-DFT form: 0.08 - 1.01).  (With a float32 pre-emphasis in front: 0.46, chirp, N = 4096.)
 #   Direct-DFT form (N <= 1024): 1.52 (dc_noise, nopad800_fbank_32k; 1.12 dc n1024_full_rows): float32 sums of up to
 #   1024 terms of one sign; committed as measured, rounded up to two decimals (the summation order inside the
 #   matrix product belongs to the BLAS build: test_calibration says so if another build needs more).

@@ -335,6 +335,32 @@ EXTRA_GEOMETRIES = {
     "nopad960_gammatone_48k": {"name": "stft", "bank": {"name": "gammatone", "scaling_function": "mel",
                                "num_filts": 24, "sampling_rate": 48000}, "frame_length_ms": 20, "use_power": True,
                                "pad_to_nearest_power_of_two": False},
+    # ---- the row buckets of stft_geoms.def the configurations above leave out (tests/flow_matrix.py) --------
+    # N = 128 with every row in use (L = 128 = 16 rows of 8)
+    "n128_full_rows_8k": {"name": "stft", "bank": {"name": "fbank", "num_filts": 14, "sampling_rate": 8000},
+                          "frame_length_ms": 16, "frame_shift_ms": 5, "use_power": True, "include_energy": True},
+    # N = 256: the fewest rows (L = 160 = 20 rows of 8), complex bank, magnitude; and every row in use (L = 256)
+    "n256_rows20_8k": {"name": "stft", "bank": {"name": "gabor", "scaling_function": "mel", "num_filts": 18,
+                       "sampling_rate": 8000}, "frame_length_ms": 20, "use_power": False},
+    "n256_full_rows_8k": {"name": "stft", "bank": {"name": "tri", "scaling_function": "mel", "num_filts": 20,
+                          "sampling_rate": 8000}, "frame_length_ms": 32, "use_power": True, "include_energy": True},
+    # N = 512: the fewest rows (L = 320 = 20 rows of 16; causal frames) and every row in use (L = 512).  (Log features:
+    # the one-launch deltas of this bucket are held to 1e-5 absolute, which float32 sums of linear powers of ~1e7
+    # cannot meet whatever the kernel)
+    "n512_rows20": {"name": "stft", "bank": {"name": "tri", "scaling_function": "mel", "num_filts": 30},
+                    "frame_length_ms": 20, "frame_style": "causal", "use_power": True, "include_energy": True},
+    "n512_full_rows": {"name": "stft", "bank": {"name": "fbank", "num_filts": 40}, "frame_length_ms": 32,
+                       "frame_shift_ms": 8, "use_power": True, "include_energy": True},
+    # N = 1024: the fewest rows (L = 800 = 50 rows of 16), and 60 rows with a mel bank (L = 960: the fixture
+    # configuration of that bucket, c5, has a dense bank, which takes none of the row-segment kernels)
+    "n1024_rows50_32k": {"name": "stft", "bank": {"name": "tri", "scaling_function": "mel", "num_filts": 64,
+                         "sampling_rate": 32000}, "frame_length_ms": 25, "use_power": True, "include_energy": True},
+    "n1024_rows60_48k": {"name": "stft", "bank": {"name": "tri", "scaling_function": "mel", "num_filts": 64,
+                         "sampling_rate": 48000}, "frame_length_ms": 20, "use_power": True, "include_energy": True},
+    # N = 2048, the 64-row bucket (L = 1764 = 56 rows of 32) with a bank whose table fits in LDS: the gammatone bank
+    # of n2048_gammatone_44k does not, and the float64 / int16 sample kernels decline it
+    "n2048_rows64_44k": {"name": "stft", "bank": {"name": "tri", "scaling_function": "mel", "num_filts": 40,
+                         "sampling_rate": 44100}, "frame_length_ms": 40, "use_power": True, "include_energy": True},
 }
 
 
