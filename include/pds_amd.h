@@ -427,6 +427,38 @@ int32_t pds_multistream_cmvn_f64(double *d_statics, double *d_pool, int64_t capa
                                  int32_t n, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * Frame stacking of batched streaming (StreamBatch(stack=...)): every num_vectors consecutive rows of a stream side by
+ * side in one row, across ticks, the reference's Stack over the stream's whole sequence of rows; data movement only
+ * (values are loaded and stored, so NaN payloads and signed zeros pass).  The rows of `capacity` streams that have not
+ * filled a group yet live in a device pool T[2][capacity][num_vectors - 1][coeffs], oldest row first: stream s's
+ * pending rows are in half h of its slot, d_pool + ((h * capacity + s) * (num_vectors - 1)) * coeffs, and a tick reads
+ * one half and writes the other (ping-pong, as the carries above: an output element and a next pending element are
+ * written by different threads while the old pending rows are read).
+ * pds_multistream_stack runs once per tick, last, after the tick's rows have been written to d_rows (rows of `coeffs`
+ * values: the statics, or the output of pds_multistream_deltas).  num_vectors >= 2.  d_meta holds n entries of 8 int64:
+ *   [0] stream s   [1] flags: bit 0 half h the pending rows are read from, bit 1 final (the stream's finalize)
+ *   [2] pending rows r (< num_vectors)   [3] new rows m   [4] first of them in d_rows (row index)
+ *   [5] groups G to write   [6] first output row in d_out (row index; rows of num_vectors * coeffs values)
+ *   [7] reserved, 0
+ * and, with seq(j) row j of the virtual sequence "r pending rows, then m new rows" (V = r + m rows), writes for g < G
+ *   d_out[[6] + g] = [seq(g * nv), .., seq(g * nv + nv - 1)]                                (nv = num_vectors)
+ * and, unless final, pool[1 - h][s][q] = seq(G * nv + q) for q < V - G * nv.  Not final: G = V / nv (rounded down), so
+ * the V % nv rows behind the groups stay pending; an entry with G = 0 copies its old pending rows to the other half and
+ * appends the new ones.  Final: nothing stays; with pad == 0 G = V / nv and the rows behind the groups are dropped,
+ * with pad != 0 G = ceil(V / nv) and seq(j) for j >= V is `fill` rounded to T (pad == 1, "constant") or seq(V - 1)
+ * (pad == 2, "edge").  G * nv - V < nv always, and only a final entry under a padding has G * nv > V; V == 0 gives
+ * G = 0.  Work is dealt by element: d_elem_prefix (int64[n + 1]) is the exclusive prefix sum of V * coeffs (final:
+ * G * nv * coeffs), total_elems its last element; n == 0 or total_elems == 0 launches nothing.  Streams of one call are
+ * distinct.  d_rows may be NULL when no entry has new rows, d_out when none has a group.
+ * --------------------------------------------------------------------------------- */
+int32_t pds_multistream_stack_f32(const float *d_rows, float *d_pool, int64_t capacity, int32_t num_vectors,
+                                  int32_t coeffs, const int64_t *d_meta, const int64_t *d_elem_prefix, int32_t n,
+                                  int64_t total_elems, int32_t pad, double fill, float *d_out, void *stream);
+int32_t pds_multistream_stack_f64(const double *d_rows, double *d_pool, int64_t capacity, int32_t num_vectors,
+                                  int32_t coeffs, const int64_t *d_meta, const int64_t *d_elem_prefix, int32_t n,
+                                  int64_t total_elems, int32_t pad, double fill, double *d_out, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Pre-processors as separate passes (reference pre.py:67-149); `preemph` above fuses the
  * first one into the frame load instead.
  * pds_preemphasize: per utterance of a packed buffer (offsets/lengths as in pds_stft_batch),

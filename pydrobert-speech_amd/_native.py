@@ -196,6 +196,12 @@ SIGNATURES = {
         c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
     "pds_multistream_cmvn_f64": (
         c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "pds_multistream_stack_f32": (
+        c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_double,
+                  c_void_p, c_void_p]),
+    "pds_multistream_stack_f64": (
+        c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_double,
+                  c_void_p, c_void_p]),
     # multi-GPU gather over RCCL
     "pds_comm_unique_id": (c_int32, [c_void_p]),
     "pds_comm_init_rank": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_void_p)]),

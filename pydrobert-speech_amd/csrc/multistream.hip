@@ -38,6 +38,16 @@
 // operation for operation; global, it normalises every row by the prior's mean and scale, computed once.  A
 // (stream, coefficient) pair belongs to one thread of the launch, which reads the pool once and writes it once, so the
 // pool needs no second half.
+//
+// Frame stacking across ticks (StreamBatch(stack=...)): multistream_stack_kernel, the last launch of a tick.  Every
+// stream of the tick is one entry of `meta` (int64[n][MK_FIELDS]).  Its virtual sequence is its `pending` rows (pool
+// half h: the rows of earlier ticks that did not fill a group, fewer than num_vectors) followed by its `fresh` new rows;
+// the entry's output is the sequence's first groups * num_vectors rows, which laid side by side in groups of
+// num_vectors are the same values in the same order -- row q of the sequence is elements q * C .. of the entry's output
+// --, and its next pending rows are the rest, written to the other half (final: none, the stream is reset).  A final
+// entry under a padding has one group more than the sequence fills: rows past its end are the fill value or the
+// sequence's last row.  Work is dealt by element as for the deltas.  Values are loaded and stored, never computed with,
+// so NaN payloads and signed zeros pass.
 #include "pds_internal.h"
 
 namespace pds {
@@ -355,6 +365,65 @@ static int32_t launch_ms_cmvn(T *d_statics, double *d_pool, int64_t capacity, in
   return PDS_OK;
 }
 
+// ---- frame stacking across ticks ------------------------------------------------------------------------------
+
+enum { MK_STREAM = 0, MK_FLAGS, MK_PENDING, MK_FRESH, MK_ROW, MK_GROUPS, MK_OUT_ROW, MK_FIELDS = 8 };
+enum { MK_FLAG_HALF = 1, MK_FLAG_FINAL = 2 };
+enum { MK_PAD_NONE = 0, MK_PAD_CONSTANT = 1, MK_PAD_EDGE = 2 };
+constexpr int MK_THREADS = 256;
+
+template <typename T>
+__global__ __launch_bounds__(MK_THREADS) void multistream_stack_kernel(
+    const T *__restrict__ rows, T *pool, int64_t capacity, int32_t nv, int32_t C, const int64_t *__restrict__ meta,
+    const int64_t *__restrict__ elem_prefix, int32_t n, int64_t total, int32_t pad, T fill, T *__restrict__ out) {
+  const int64_t g = (int64_t)blockIdx.x * MK_THREADS + threadIdx.x;
+  if (g >= total) return;
+  // entry of this element: the last e with elem_prefix[e] <= g (entries without elements are passed over)
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (elem_prefix[mid] <= g) lo = mid; else hi = mid;
+  }
+  const int64_t *m = meta + (int64_t)lo * MK_FIELDS;
+  const int64_t s = m[MK_STREAM], half = m[MK_FLAGS] & MK_FLAG_HALF, pending = m[MK_PENDING];
+  const int64_t V = pending + m[MK_FRESH];  // (> 0: an entry with elements has a row to show or to keep)
+  const int64_t slot = (int64_t)(nv - 1) * C;
+  const T *pin = pool + (half * capacity + s) * slot;
+  const int64_t fresh_at = m[MK_ROW] - pending;  // `rows` row of row v >= pending of the sequence: fresh_at + v
+  const int64_t l = g - elem_prefix[lo];
+  const int64_t q = l / C;  // row of the sequence, or past its end in a padded last group
+  const int i = (int)(l - q * C);
+  auto row = [&](int64_t v) -> T { return v < pending ? pin[v * C + i] : rows[(fresh_at + v) * C + i]; };
+  const int64_t shown = m[MK_GROUPS] * nv;
+  if (q >= shown) {  // a row of the next pending ones: the sequence's rows behind the groups (none after a finalize)
+    if (m[MK_FLAGS] & MK_FLAG_FINAL) return;
+    pool[((1 - half) * capacity + s) * slot + (q - shown) * C + i] = row(q);
+    return;
+  }
+  // (rows of one group lie side by side: the entry's output is its sequence, element for element)
+  out[m[MK_OUT_ROW] * ((int64_t)nv * C) + l] = q < V ? row(q) : (pad == MK_PAD_EDGE ? row(V - 1) : fill);
+}
+
+template <typename T>
+static int32_t launch_ms_stack(const T *d_rows, T *d_pool, int64_t capacity, int32_t num_vectors, int32_t coeffs,
+                               const int64_t *d_meta, const int64_t *d_elem_prefix, int32_t n, int64_t total_elems,
+                               int32_t pad, double fill, T *d_out, void *stream) {
+  if (n < 0 || total_elems < 0 || capacity < 0 || num_vectors < 2 || coeffs <= 0)
+    return invalid_ms("multistream_stack: bad size");
+  if (pad != MK_PAD_NONE && pad != MK_PAD_CONSTANT && pad != MK_PAD_EDGE)
+    return invalid_ms("multistream_stack: pad must be 0 (none), 1 (constant) or 2 (edge)");
+  if (n == 0 || total_elems == 0) return PDS_OK;
+  const int64_t blocks = (total_elems + MK_THREADS - 1) / MK_THREADS;
+  if (blocks > 0x7fffffff) return invalid_ms("multistream_stack: too many elements in one call");
+  // (d_rows / d_out may be null in a tick without new rows / without a full group: only pending rows move)
+  if (!d_pool || !d_meta || !d_elem_prefix) return invalid_ms("multistream_stack: null pointer");
+  hipLaunchKernelGGL(multistream_stack_kernel<T>, dim3((unsigned)blocks), dim3(MK_THREADS), 0, (hipStream_t)stream,
+                     d_rows, d_pool, capacity, num_vectors, coeffs, d_meta, d_elem_prefix, n, total_elems, pad, (T)fill,
+                     d_out);
+  PDS_HIP(hipGetLastError());
+  return PDS_OK;
+}
+
 }  // namespace pds
 
 extern "C" {
@@ -418,6 +487,19 @@ int32_t pds_multistream_cmvn_f64(double *d_statics, double *d_pool, int64_t capa
                                  const double *d_prior, int32_t norm_var, int32_t running, const int64_t *d_meta,
                                  int32_t n, void *stream) {
   return pds::launch_ms_cmvn<double>(d_statics, d_pool, capacity, coeffs, d_prior, norm_var, running, d_meta, n, stream);
+}
+
+int32_t pds_multistream_stack_f32(const float *d_rows, float *d_pool, int64_t capacity, int32_t num_vectors,
+                                  int32_t coeffs, const int64_t *d_meta, const int64_t *d_elem_prefix, int32_t n,
+                                  int64_t total_elems, int32_t pad, double fill, float *d_out, void *stream) {
+  return pds::launch_ms_stack<float>(d_rows, d_pool, capacity, num_vectors, coeffs, d_meta, d_elem_prefix, n,
+                                     total_elems, pad, fill, d_out, stream);
+}
+int32_t pds_multistream_stack_f64(const double *d_rows, double *d_pool, int64_t capacity, int32_t num_vectors,
+                                  int32_t coeffs, const int64_t *d_meta, const int64_t *d_elem_prefix, int32_t n,
+                                  int64_t total_elems, int32_t pad, double fill, double *d_out, void *stream) {
+  return pds::launch_ms_stack<double>(d_rows, d_pool, capacity, num_vectors, coeffs, d_meta, d_elem_prefix, n,
+                                      total_elems, pad, fill, d_out, stream);
 }
 
 }  // extern "C"

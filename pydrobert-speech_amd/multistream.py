@@ -13,6 +13,7 @@ samples of up to `capacity` streams in a device pool and takes every stream that
     sb = StreamBatch(computer, capacity=4096, deltas=Deltas(2))   # statics + delta + delta-delta, see below
     sb = StreamBatch(computer, capacity=4096, preemphasis=0.97)   # Preemphasize(0.97) over every stream's whole signal
     sb = StreamBatch(computer, capacity=4096, cmvn=Standardize())  # running CMVN per stream, see below
+    sb = StreamBatch(computer, capacity=4096, stack=Stack(3))      # every 3 rows of a stream side by side, see below
 
 Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
 the same chunks: the same row counts, dtype and -- for float32 and float64 samples -- the same values bit for bit as
@@ -32,9 +33,9 @@ Both kinds of tick, of this class and of :class:`multistream_si.SiStreamBatch`, 
 :func:`_TickBatch._tick`: the streams' spans (where each one's samples lie in what the feature launch reads), the
 upload -- laid out by :func:`_tick_layout` and addressed by section name through :class:`_Upload`, nowhere by hand --,
 the assemble launch (``compute_chunks`` only), the feature launch, the commit or reset of the host state, then the
-cmvn and the deltas launch.  A class adds what differs through four hooks: its host state, the order in which the
-emitting streams launch, its extra rows of launch metadata, and the feature launch itself.  A new stage is one edit
-there.
+cmvn, the deltas and the stack launch.  A class adds what differs through four hooks: its host state, the order in
+which the emitting streams launch, its extra rows of launch metadata, and the feature launch itself.  A new stage is
+one edit there.
 
 With `deltas` (a :class:`post.Deltas`: "edge" padding, concatenated along the coefficient axis) a stream's rows are
 those of ``deltas.apply(X, axis=0)`` over the whole sequence X of its statics, bit for bit, delayed by the look-ahead
@@ -78,6 +79,21 @@ returns the stream to P.  With `deltas` the deltas are taken of the normalised s
 add-deltas``), so the history pool holds normalised rows and a stream's rows are ``deltas.apply(Y, axis=0)``.
 :func:`StreamBatch.cmvn_stats` returns the streams' current tables.
 
+With `stack` (a :class:`post.Stack`: frames along the row axis, ``pad_mode`` None, "edge" or "constant") every
+``nv = num_vectors`` consecutive rows of a stream become one row of ``nv`` times the width -- the last stage, after
+`cmvn` and `deltas`: a stream's rows, concatenated over its ``compute_chunks`` calls and its ``finalize``, are
+``stack.apply(X, axis=-1)`` of the sequence X of rows the same object returns without `stack`, bit for bit (the stage
+moves values and computes nothing, so NaN payloads and signed zeros pass).  Groups run on across ticks: a stream holds
+``r < nv`` pending rows, those not yet returned; a tick that brings it m rows returns ``(r + m) // nv`` stacked rows
+and keeps the other ``(r + m) % nv``; ``finalize`` returns the groups of what is left and drops the remainder
+(``pad_mode=None``, as the reference does) or fills the last group with the stream's last row ("edge") or a constant
+("constant", ``constant_values`` rounded to `dtype`), and nothing where nothing is left.  The other numpy pad modes look
+at the whole utterance and are refused.  :class:`StackState` counts the pending rows per stream on the host; the device
+keeps them in a ping-pong pool of ``2 * capacity * (nv - 1)`` rows, and one launch per tick
+(``pds_multistream_stack_*``), the last, reads "pending rows, then the tick's new rows", writes the groups and the next
+pending rows.  The row offsets of the packed calls count stacked rows; :attr:`StreamBatch.lookahead` stays the delay of
+the deltas, in frames.
+
 Not thread-safe; works on the current torch stream of the device that was current at construction.
 """
 import functools
@@ -88,15 +104,17 @@ import numpy as np
 from . import _native, config
 from .alias import alias_factory_subclass_from_arg
 from .compute import PackedLayout, ShortTimeFourierTransformFrameComputer
-from .post import Deltas, PostProcessor, Standardize
+from .post import Deltas, PostProcessor, Stack, Standardize
 from .pre import Preemphasize, PreProcessor
 
-__all__ = ["CmvnState", "DeltaState", "StreamBatch", "StreamState", "streaming_cmvn", "streaming_deltas",
-           "streaming_preemphasis"]
+__all__ = ["CmvnState", "DeltaState", "StackState", "StreamBatch", "StreamState", "streaming_cmvn",
+           "streaming_deltas", "streaming_preemphasis", "streaming_stack"]
 
 _FIELDS = 8  # int64 per entry of pds_multistream_assemble's metadata (include/pds_amd.h)
 _DFIELDS = 8  # ... and of pds_multistream_deltas'
 _CFIELDS = 8  # ... and of pds_multistream_cmvn's
+_KFIELDS = 8  # ... and of pds_multistream_stack's
+_PAD_NONE, _PAD_CONSTANT, _PAD_EDGE = 0, 1, 2  # the `pad` of pds_multistream_stack
 _FLAG_FRESH = 1  # of the flags word of the cmvn metadata: the stream starts from the prior statistics
 _FLAG_FINAL = 2  # (bit 0 of the flags word is the pool half)
 _HAS_SAMPLE = 2  # of word 7 of the assemble metadata, beside the pool half in bit 0: the stream has a previous sample
@@ -441,6 +459,118 @@ class CmvnState:
         meta[:, 5:] = 0
 
 
+def streaming_stack(stack) -> Optional[Tuple[Stack, int, int, float]]:
+    """`stack` as :class:`StreamBatch` takes it -- a :class:`post.Stack` or what
+    ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one -> ``(Stack, num_vectors, pad, fill)`` with `pad`
+    as pds_multistream_stack takes it (0 none, 1 constant, 2 edge) and `fill` the constant (0.0 unless given), or None
+    for no stacking (``stack=None`` or ``num_vectors == 1``); ``ValueError`` for settings batched streaming does not
+    serve"""
+    if stack is None:
+        return None
+    try:
+        stack = alias_factory_subclass_from_arg(PostProcessor, stack)
+    except (KeyError, TypeError) as e:
+        raise ValueError(f"StreamBatch: stack is no post-processor ({e!r})") from None
+    if not isinstance(stack, Stack):
+        raise ValueError("StreamBatch: stack must be a post.Stack")
+    nv = stack.num_vectors
+    if isinstance(nv, (bool, np.bool_)) or not isinstance(nv, (int, np.integer)) or nv < 1:
+        raise ValueError("StreamBatch: num_vectors must be a positive integer")
+    if isinstance(stack.time_axis, (bool, np.bool_)) or stack.time_axis not in (0, -2):
+        raise ValueError("StreamBatch: the stack's time axis must be the row axis of (rows, coeffs): 0 or -2")
+    mode, kwargs = stack._pad_mode, stack._pad_kwargs
+    fill = 0.0
+    if mode is None:
+        pad = _PAD_NONE
+    elif isinstance(mode, str) and mode == "edge":
+        pad = _PAD_EDGE
+    elif isinstance(mode, str) and mode == "constant":
+        pad = _PAD_CONSTANT
+    else:
+        raise ValueError(f"StreamBatch: stack must use pad_mode None, 'edge' or 'constant', not {mode!r}: the other "
+                         "numpy pad modes need the whole utterance, which a stream does not have -- stack after "
+                         "finalize")
+    if kwargs and (pad != _PAD_CONSTANT or set(kwargs) != {"constant_values"}):
+        raise ValueError("StreamBatch: the only pad argument of stack is a scalar constant_values with "
+                         "pad_mode='constant'")
+    if kwargs:
+        value = kwargs["constant_values"]
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise ValueError("StreamBatch: the stack's constant_values must be a scalar number")
+        fill = float(value)
+    if nv == 1:
+        return None
+    return stack, int(nv), pad, fill
+
+
+class StackState:
+    """Host bookkeeping of the frame stacking of many streams.  Needs no device.
+
+    `num_vectors` rows make a group; `pad`: a ``finalize`` fills a last, partial group instead of dropping it.  Per
+    stream: ``pending`` rows given to the stage but not returned yet (always < `num_vectors`; they lie in the device
+    pool, oldest first) and ``half`` the pool half holding them.
+    """
+
+    def __init__(self, capacity: int, num_vectors: int, pad: bool = False):
+        capacity, num_vectors = int(capacity), int(num_vectors)
+        if capacity <= 0 or num_vectors <= 0:
+            raise ValueError("capacity and num_vectors must be positive")
+        self.capacity, self.nv, self.pad = capacity, num_vectors, bool(pad)
+        self.pool_rows = num_vectors - 1
+        self.pending = np.zeros(capacity, dtype=np.int64)
+        self.half = np.zeros(capacity, dtype=np.int64)
+
+    def step(self, ids: np.ndarray, m: np.ndarray, final: bool = False) -> dict:
+        """What a tick that brings streams `ids` `m` new rows does, without changing the state.  Per stream, over the
+        virtual sequence "`pending` rows, then `m` new rows": `groups` stacked rows (the whole groups of the sequence;
+        if `final` under a padding a last partial one too), `keep` rows of next pending ones (the sequence's rows behind
+        the groups; none if `final`) and the `half` the pending rows are read from"""
+        nv = self.nv
+        m = np.asarray(m, dtype=np.int64)
+        pending, half = self.pending[ids], self.half[ids]
+        V = pending + m
+        padded = final and self.pad
+        groups = (V + (nv - 1)) // nv if padded else V // nv
+        rest = V - groups * nv  # rows of the sequence behind the groups; negative: rows the last group lacks
+        keep = np.zeros_like(V) if final else rest
+        # the kernel reads row q of the sequence for every q < groups * nv + keep.  All of them are in the sequence --
+        # and what is kept fits the pool -- unless a finalize pads: then fewer than a group's are not, and the
+        # sequence has a last row to repeat (no rows give no group)
+        assert len(m) == 0 or m.min() >= 0
+        if padded:
+            assert ((rest <= 0) & (rest > -nv) & ((V > 0) | (groups == 0))).all()
+        else:
+            assert ((rest >= 0) & (rest <= self.pool_rows)).all()
+        return dict(pending=pending, m=m, groups=groups, keep=keep, half=half, final=bool(final))
+
+    def commit(self, ids: np.ndarray, step: dict) -> None:
+        if step["final"]:
+            self.reset(ids)
+            return
+        self.pending[ids] = step["keep"]
+        self.half[ids] = step["half"] ^ 1  # (the stack kernel wrote the next pending rows to the other half)
+
+    def reset(self, ids: np.ndarray) -> None:
+        self.pending[ids] = 0
+
+    def fill_meta(self, meta: np.ndarray, prefix: np.ndarray, ids: np.ndarray, step: dict, new_rows: np.ndarray,
+                  out_rows: np.ndarray, coeffs: int) -> int:
+        """pds_multistream_stack's metadata of a tick into `meta` (int64[n, 8]) and `prefix` (int64[n + 1], elements
+        per entry as an exclusive prefix sum); `new_rows` / `out_rows`: each stream's first row in the tick's rows and
+        in its output.  Returns the number of elements"""
+        meta[:, 0] = ids
+        meta[:, 1] = step["half"] | (_FLAG_FINAL if step["final"] else 0)
+        meta[:, 2] = step["pending"]
+        meta[:, 3] = step["m"]
+        meta[:, 4] = new_rows
+        meta[:, 5] = step["groups"]
+        meta[:, 6] = out_rows
+        meta[:, 7] = 0
+        prefix[0] = 0
+        np.cumsum((step["groups"] * self.nv + step["keep"]) * int(coeffs), out=prefix[1:])
+        return int(prefix[-1])
+
+
 class _Upload:
     """A tick's one upload, in int64 words: `sample_words` of samples, then the sections of `layout`
     (:func:`_place`) back to back.  `words` is the sum: what the tick asks of the staging and what it sends.  The
@@ -490,17 +620,19 @@ def _place(sections):
 
 
 @functools.lru_cache(maxsize=256)  # (a batch's ticks repeat a few sizes: each is placed once)
-def _tick_layout(n, E, launch_rows, chunks, deltas, cmvn):
+def _tick_layout(n, E, launch_rows, chunks, deltas, cmvn, stack=False):
     """The sections behind the samples in the upload of a tick over `n` streams of which `E` emit frames, placed: the
     assemble metadata and the tile prefix (`chunks`: a ``compute_chunks`` tick; ``finalize`` has neither, and no
     samples), the launch metadata -- `launch_rows` rows, one column per emitting stream --, the deltas metadata and
-    the element prefix (`deltas`), the cmvn metadata (`cmvn`)"""
+    the element prefix (`deltas`), the cmvn metadata (`cmvn`), the stack metadata and its element prefix (`stack`)"""
+    # (a batch without `stack` has the layout it had before there was one: the two sections are not placed at all)
     return _place((("assemble", (n if chunks else 0, _FIELDS)),
                    ("tiles", (n + 1 if chunks else 0,)),
                    ("launch", (launch_rows, E)),
                    ("deltas", (n if deltas else 0, _DFIELDS)),
                    ("elems", (n + 1 if deltas else 0,)),
-                   ("cmvn", (n if cmvn else 0, _CFIELDS))))
+                   ("cmvn", (n if cmvn else 0, _CFIELDS)))
+                  + ((("stack", (n, _KFIELDS)), ("stack_elems", (n + 1,))) if stack else ()))
 
 
 class _TickBatch:
@@ -516,7 +648,7 @@ class _TickBatch:
     _launch_extra = ()
 
     def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None, cmvn=None,
-                 cmvn_running=True):
+                 cmvn_running=True, stack=None):
         # every argument is read before a device is touched
         if not isinstance(computer, self._computer_type):
             raise TypeError(self._wrong_computer)
@@ -525,10 +657,11 @@ class _TickBatch:
             raise TypeError("StreamBatch: samples must be float32 or float64")
         spec, coeff = streaming_deltas(deltas), streaming_preemphasis(preemphasis)
         cspec = streaming_cmvn(cmvn, bool(cmvn_running), computer.num_coeffs)
+        kspec = streaming_stack(stack)
         self.state, row_length = self._new_state(computer, capacity)
         # the device side: `computer`'s plan, the carry pool of ``2 * capacity * row_length`` samples, the
-        # previous-sample pool (with a pre-emphasis), the staging buffers, the history pool of the deltas and the pool
-        # of running sums of the cmvn
+        # previous-sample pool (with a pre-emphasis), the staging buffers, the history pool of the deltas, the pool of
+        # running sums of the cmvn and the pool of pending rows of the stack
         torch = _native.require_device()
         self._torch = torch
         self._lib = _native.lib()
@@ -536,7 +669,7 @@ class _TickBatch:
         self.capacity = self.state.capacity
         self.device = torch.device("cuda", torch.cuda.current_device())
         self._F = computer.num_coeffs  # statics per row
-        self.num_coeffs = self._F
+        self._C = self._F  # ... and coefficients per row before stacking
         self._comp = computer
         self._plan = computer._native_plan(self.device)
         self._tdtype = torch.float32 if dtype == np.float32 else torch.float64
@@ -559,7 +692,7 @@ class _TickBatch:
         if spec is not None:
             self._deltas, self._K, W = spec
             self.dstate = DeltaState(self.capacity, self._K * W)
-            self.num_coeffs = (self._K + 1) * self._F
+            self._C = (self._K + 1) * self._F
             self._hist = torch.zeros((2, self.capacity, self.dstate.hist_rows, self._F), dtype=self._tdtype,
                                      device=self.device)
             self._d_filts, self._d_filt_off = self._deltas._filters_on(self.device)
@@ -576,6 +709,17 @@ class _TickBatch:
                 self._sums = torch.empty((self.capacity, 2, self._F), dtype=torch.float64, device=self.device)
             self._cmvn_fn = (self._lib.pds_multistream_cmvn_f32 if dtype == np.float32
                              else self._lib.pds_multistream_cmvn_f64)
+        self.num_coeffs = self._C
+        self.kstate = self._pending = None
+        if kspec is not None:
+            self._stack, nv, self._pad, fill = kspec
+            self._fill = float(dtype.type(fill))  # (rounded to `dtype` as numpy.pad rounds it)
+            self.kstate = StackState(self.capacity, nv, self._pad != _PAD_NONE)
+            self.num_coeffs = nv * self._C
+            # every stream's pending rows (a stream without any has nothing read from its slot: no fill)
+            self._pending = torch.empty((2, self.capacity, nv - 1, self._C), dtype=self._tdtype, device=self.device)
+            self._stack_fn = (self._lib.pds_multistream_stack_f32 if dtype == np.float32
+                              else self._lib.pds_multistream_stack_f64)
 
     # ---- public interface -----------------------------------------------------------
 
@@ -583,6 +727,11 @@ class _TickBatch:
     def lookahead(self) -> int:
         """frames of delay of the rows: ``num_deltas * context_window`` (0 without deltas)"""
         return self.dstate.H if self.dstate is not None else 0
+
+    @property
+    def num_vectors(self) -> int:
+        """rows of a stream side by side in a returned row (1 without `stack`)"""
+        return self.kstate.nv if self.kstate is not None else 1
 
     def started(self, ids) -> np.ndarray:
         """bool per stream of `ids`: between its first chunk and its ``finalize``"""
@@ -659,7 +808,7 @@ class _TickBatch:
 
     def close(self) -> None:
         """Release the pools and the pinned buffers; the object cannot be used afterwards"""
-        self._pool = self._hist = self._prev = self._sums = self._d_prior = None
+        self._pool = self._hist = self._prev = self._sums = self._d_prior = self._pending = None
         self._up = [None, None]
         self._up_events = [None, None]
         self._down = None
@@ -751,7 +900,7 @@ class _TickBatch:
         row0 = rows[:-1]
         order = self._emit_order(step, np.flatnonzero(k > 0))
         up = _Upload(ns, _tick_layout(n, len(order), 4 + len(self._launch_extra), not final, self.dstate is not None,
-                                      self.cstate is not None))
+                                      self.cstate is not None, self.kstate is not None))
         slot, buf = self._staging(up.words)
         up.pinned = buf.numpy()
         if ns:
@@ -780,6 +929,12 @@ class _TickBatch:
         if self.cstate is not None:
             cstep = self.cstate.step(ids, k, final=final)
             self.cstate.fill_meta(up.host("cmvn"), ids, cstep, row0)
+        if self.kstate is not None:  # over what the stages before it return: the statics, or the rows of the deltas
+            new = dstep["out_rows"] if self.dstate is not None else rows
+            kstep = self.kstate.step(ids, np.diff(new), final=final)
+            kstep["out_rows"] = _exclusive_cumsum(kstep["groups"])
+            kelems = self.kstate.fill_meta(up.host("stack"), up.host("stack_elems"), ids, kstep, new[:-1],
+                                           kstep["out_rows"][:-1], self._C)
         stream = self._torch.cuda.current_stream(self.device)
         up.device = self._send(slot, up.words, stream)
         if final:
@@ -796,7 +951,9 @@ class _TickBatch:
         if self.cstate is not None:
             self._cmvn_launch(feats, up.dev("cmvn"), ids, cstep, stream)
         if self.dstate is not None:
-            return self._delta_launch(feats, up.dev("deltas"), up.dev("elems"), ids, dstep, elems, stream)
+            feats, rows = self._delta_launch(feats, up.dev("deltas"), up.dev("elems"), ids, dstep, elems, stream)
+        if self.kstate is not None:
+            return self._stack_launch(feats, up.dev("stack"), up.dev("stack_elems"), ids, kstep, kelems, stream)
         return feats, rows
 
     def _assemble_launch(self, samples, i16, d_meta, d_tile_prefix, n, tiles, work_len, stream):
@@ -830,13 +987,25 @@ class _TickBatch:
     def _delta_launch(self, statics, d_meta, d_elem_prefix, ids, dstep, elems, stream):
         """one pds_multistream_deltas launch over the tick's `statics`: the rows due and the next histories"""
         rows = dstep["out_rows"]
-        out = self._torch.empty((int(rows[-1]), self.num_coeffs), dtype=self._tdtype, device=self.device)
+        out = self._torch.empty((int(rows[-1]), self._C), dtype=self._tdtype, device=self.device)
         rc = self._deltas_fn(statics.data_ptr() if statics.shape[0] else None, self._hist.data_ptr(), self.capacity,
                              self.dstate.hist_rows, self._F, self._d_filts.data_ptr(), self._d_filt_off.data_ptr(),
                              self._K, d_meta.data_ptr(), d_elem_prefix.data_ptr(), len(ids), elems, out.data_ptr(),
                              stream.cuda_stream)
         _native.check(rc, "pds_multistream_deltas")
         self.dstate.commit(ids, dstep)
+        return out, rows
+
+    def _stack_launch(self, new, d_meta, d_elem_prefix, ids, kstep, elems, stream):
+        """one pds_multistream_stack launch over the tick's `new` rows: the groups that are full and the next pending
+        rows"""
+        rows = kstep["out_rows"]
+        out = self._torch.empty((int(rows[-1]), self.num_coeffs), dtype=self._tdtype, device=self.device)
+        rc = self._stack_fn(new.data_ptr() if new.shape[0] else None, self._pending.data_ptr(), self.capacity,
+                            self.kstate.nv, self._C, d_meta.data_ptr(), d_elem_prefix.data_ptr(), len(ids), elems,
+                            self._pad, self._fill, out.data_ptr() if out.shape[0] else None, stream.cuda_stream)
+        _native.check(rc, "pds_multistream_stack")
+        self.kstate.commit(ids, kstep)
         return out, rows
 
     def _to_host(self, feats, rows, started) -> List[np.ndarray]:
@@ -893,6 +1062,18 @@ class StreamBatch(_TickBatch):
     The statistics' count must be a whole number.  ``finalize`` returns a stream to the statistics passed in;
     :func:`cmvn_stats` reads a stream's current ones.  The ``Standardize`` itself is not changed.  Additional device
     memory: the running sums, ``2 * capacity * F`` float64 (none with ``cmvn_running=False``).
+
+    `stack`: a :class:`post.Stack` (or what ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one:
+    ``{"name": "stack", "num_vectors": 3}``) with the row axis as time axis (0 or -2) and ``pad_mode`` None, "edge" or
+    "constant" (with at most a scalar ``constant_values``); ``None`` or ``num_vectors == 1``: no stacking.  The last
+    stage: with C the row width after `cmvn` and `deltas` and ``nv = num_vectors`` (:attr:`num_vectors`) every stream's
+    rows become those of ``stack.apply(X, axis=-1)`` over the sequence X of its rows without `stack`
+    (``num_coeffs == nv * C``), bit for bit, groups running on across calls: when a stream holds r rows not yet
+    returned and a call brings it m, ``compute_chunks`` returns ``(r + m) // nv`` rows and keeps ``(r + m) % nv``;
+    ``finalize`` returns ``(r + m) // nv`` and drops the rest, or under a padding ``ceil((r + m) / nv)`` with the last
+    group filled up.  The row offsets of the packed calls count stacked rows.  Additional device memory: the pool of
+    pending rows, ``2 * capacity * (nv - 1) * C`` elements of `dtype`, and per tick the ``(new rows, C)`` rows before
+    stacking.
 
     Under ``config.FLOAT64_ARITHMETIC == "float32"`` float64 samples are rounded to float32 once in the work buffer
     (after a pre-emphasis, which works in float64) and the float32 features widened (within the float32 tolerance of

@@ -11,6 +11,7 @@
 
     sb = SiStreamBatch(computer, capacity=4096, deltas=Deltas(2), preemphasis=0.97)   # as for StreamBatch
     sb = SiStreamBatch(computer, capacity=4096, cmvn=Standardize(), cmvn_running=True)  # as for StreamBatch
+    sb = SiStreamBatch(computer, capacity=4096, stack=Stack(3))                         # as for StreamBatch
 
 Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
 the same chunks: the same row counts, dtype and -- for float32 and float64 samples alike -- the same values bit for
@@ -28,7 +29,9 @@ cmvn.apply(x)`` frame by frame -- cumulative mean and variance normalisation, on
 any -- or global (``cmvn_running=False``), ``cmvn.apply(x)`` with those fixed statistics; float64, bit for bit, rounded
 to `dtype` once; a stream's first frame without a prior is a row of zeros, a NaN stays in its stream's sums until the
 ``finalize``, the reference's "0 variance" warning is not raised, and deltas are taken of the normalised statics.  The
-arithmetic is spelled out in :mod:`multistream`.
+arithmetic is spelled out in :mod:`multistream`.  With `stack` (a :class:`post.Stack`) every ``num_vectors`` consecutive
+rows of a stream, after `cmvn` and `deltas`, are returned side by side as one, groups running on across ticks: the
+stream's rows are ``stack.apply`` of its rows without `stack`, bit for bit, as documented in :mod:`multistream`.
 
 A tick: :class:`SiStreamState` -- the array form of ``si.py``'s ``compute_chunk`` / ``_emit`` / ``finalize``
 bookkeeping -- is advanced on the host, which fixes every size without reading the device; samples and metadata go up
@@ -36,10 +39,10 @@ in one copy from pinned memory; one ``pds_multistream_assemble_*`` launch writes
 + chunk of every stream) and the new carries into the other pool half; one ``pds_si_batch_starts_*`` call computes
 the frames of every stream that has any, each continued at its own `start` (float32: the plan's overlap-save form
 when it has one, else direct filtering; float64: direct filtering -- the choices the single-stream computer makes);
-optionally one ``pds_multistream_cmvn_*`` launch and one ``pds_multistream_deltas_*`` launch, in that order; one
-download.  ``finalize`` reads the carries where they lie in the pool.  The pipeline is :func:`multistream._TickBatch._tick`,
-shared with ``StreamBatch``; this module adds the state, the tick order of the emitting streams, the `start` row of the
-launch metadata and the ``pds_si_batch_starts_*`` call.
+optionally one ``pds_multistream_cmvn_*`` launch, one ``pds_multistream_deltas_*`` launch and one
+``pds_multistream_stack_*`` launch, in that order; one download.  ``finalize`` reads the carries where they lie in the
+pool.  The pipeline is :func:`multistream._TickBatch._tick`, shared with ``StreamBatch``; this module adds the state,
+the tick order of the emitting streams, the `start` row of the launch metadata and the ``pds_si_batch_starts_*`` call.
 
 The per-utterance start is what makes one call enough.  A stream's `start` is ``skip0 - lead + done * S - tail_at``:
 the position of its next frame's first integrated sample, relative to the first sample it still keeps.  Once
@@ -179,12 +182,13 @@ class SiStreamBatch(_TickBatch):
     """``compute_chunk`` / ``finalize`` of many streams of one short-integration computer, one tick per call
 
     `computer`: a :class:`si.ShortIntegrationFrameComputer` (its plan and configuration are used; its own streaming
-    state is not touched).  `capacity`, `dtype`, `deltas`, `preemphasis`, `cmvn`, `cmvn_running` and every method
-    (``cmvn_stats`` among them): as :class:`multistream.StreamBatch` -- with `cmvn` the static rows are standardised
-    frame by frame, running or by fixed statistics, before the deltas are taken.  Device memory: the carry pool,
-    ``2 * capacity * row_length`` samples with ``row_length = max(max_support - 1, skip0) + 2 * frame_shift``
-    (:attr:`SiStreamState.row_length`), plus what `deltas`, `preemphasis` and `cmvn` (the running sums,
-    ``2 * capacity * F`` float64) add there, and per tick the work buffer and, for float32 with the overlap-save form, its
+    state is not touched).  `capacity`, `dtype`, `deltas`, `preemphasis`, `cmvn`, `cmvn_running`, `stack` and every
+    method (``cmvn_stats`` among them): as :class:`multistream.StreamBatch` -- with `cmvn` the static rows are
+    standardised frame by frame, running or by fixed statistics, before the deltas are taken, and with `stack` the rows
+    are stacked last.  Device memory: the carry pool, ``2 * capacity * row_length`` samples with
+    ``row_length = max(max_support - 1, skip0) + 2 * frame_shift`` (:attr:`SiStreamState.row_length`), plus what
+    `deltas`, `preemphasis`, `cmvn` (the running sums, ``2 * capacity * F`` float64) and `stack` (the pending rows) add
+    there, and per tick the work buffer and, for float32 with the overlap-save form, its
     scratch (``pds_si_scratch_len`` of the tick's streams and its largest frame count).
     """
 
