@@ -594,6 +594,19 @@ int64_t pds_si_scratch_len(const pds_si_plan *plan, int32_t B, int64_t max_frame
  * for shorter supports when it wastes less of a transform on the overlap), or 0 when the supports
  * are too long for it and float32 takes the direct form as well */
 int32_t pds_si_plan_fft_size(const pds_si_plan *plan);
+/* The shape of the launch pds_si_batch_* makes for B utterances of at most max_frames frames (host arithmetic only,
+ * no HIP call; for tests and tuning).  `direct` != 0: the direct form, as taken by float64, by a null d_scratch and by
+ * plans without an FFT form (those report it whatever `direct` says).  out (host, int32[8]):
+ *   [0] form: 1024 or 2048 (transform size of the overlap-save form), 0 for the direct form
+ *   [1] grid.x (grid.y is B)
+ *   [2] groups = grid.z: workgroups the filters of one stretch are dealt to (direct: 1)
+ *   [3] c_per_group: filters a workgroup walks, the last group possibly fewer (direct: num_coeffs)
+ *   [4] shift-sized blocks a transform yields (direct: JB, the blocks of a workgroup's tile)
+ *   [5] window factors a lane keeps per window half: 3, 5, 8 or 16 (direct: passes of the thread block over a tile)
+ *   [6] transforms per workgroup: 16 or 8 (direct: JB - 1, the frames a workgroup writes)
+ *   [7] compute units the split was sized for, cached at plan creation (0 for plans without an FFT form)
+ * PDS_ERR_INVALID for a null plan or out, B outside 1 .. 65535 or max_frames < 1. */
+int32_t pds_si_launch_shape(const pds_si_plan *plan, int32_t B, int64_t max_frames, int32_t direct, int32_t *out);
 int32_t pds_si_batch_f32(const pds_si_plan *plan, const float *d_signal, const int64_t *d_offsets,
                          const int64_t *d_lengths, const int64_t *d_nframes,
                          const int64_t *d_row_off, int32_t B, int64_t max_frames, int64_t start,

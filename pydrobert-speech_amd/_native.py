@@ -149,6 +149,7 @@ SIGNATURES = {
     "pds_si_plan_destroy": (None, [c_void_p]),
     "pds_si_scratch_len": (c_int64, [c_void_p, c_int32, c_int64]),
     "pds_si_plan_fft_size": (c_int32, [c_void_p]),
+    "pds_si_launch_shape": (c_int32, [c_void_p, c_int32, c_int64, c_int32, POINTER(c_int32)]),
     "pds_si_batch_f32": (c_int32, _SI_BATCH_ARGS[:9] + [c_void_p] + _SI_BATCH_ARGS[9:]),
     "pds_si_batch_f64": (c_int32, _SI_BATCH_ARGS),
     # ... with d_starts (one start per utterance) behind d_row_off and no scalar start

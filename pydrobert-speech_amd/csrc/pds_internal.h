@@ -109,6 +109,8 @@ namespace pds {
 int32_t si_fft_tables_create(pds_si_plan *plan, const double *taps);
 void si_fft_tables_destroy(pds_si_plan *plan);
 int64_t si_fft_scratch_len(const pds_si_plan *plan, int32_t B, int64_t max_frames);
+struct SiFftShape;  // si_shape.h
+SiFftShape si_fft_shape_of(const pds_si_plan *plan, int32_t B, int64_t max_frames);  // (plans with the FFT form)
 // (d_starts: one start per utterance, or null: `start` for all of them)
 int32_t launch_si_fft(const pds_si_plan *plan, const float *d_signal, const int64_t *d_offsets,
                       const int64_t *d_lengths, const int64_t *d_nframes, const int64_t *d_row_off,

@@ -24,9 +24,11 @@
 // Arithmetic is the signal's own precision (float or double), as for the STFT kernels.  Work is
 // O(M) per sample and filter; an overlap-save FFT variant is the obvious next step for banks with
 // supports in the thousands of samples.
+#include <algorithm>
 #include <vector>
 
 #include "pds_internal.h"
+#include "si_shape.h"
 
 namespace pds {
 
@@ -35,8 +37,7 @@ static int32_t invalid_si(const char *msg) {
   return PDS_ERR_INVALID;
 }
 
-constexpr int kSiR = 9;          // consecutive samples per thread
-constexpr int kSiThreads = 256;
+// (kSiR = 9 consecutive samples per thread, kSiThreads = 256: si_shape.h)
 
 template <typename T>
 struct SiArgs {
@@ -165,11 +166,8 @@ static int32_t launch_si(const pds_si_plan *plan, const T *d_signal, const int64
   if (out_stride < d.num_coeffs) return invalid_si("si_batch: out_stride < num_coeffs");
   if (int32_t rc = check_plan_device(plan->device, "si_batch"); rc != PDS_OK) return rc;
   const int S = d.frame_shift;
-  int JB = (kSiThreads * kSiR) / S;
-  if (JB < 2) JB = 2;  // long shifts: two blocks per tile, several passes of the thread block
-  if ((int64_t)JB - 1 > max_frames) JB = (int)max_frames + 1;
-  const int tile = JB * S;
-  const size_t smem = ((size_t)tile + plan->mpad - 1 + kSiR + 2 * (size_t)tile + 2 * (size_t)JB) * sizeof(T);
+  const SiDirectShape shape = si_direct_shape(S, plan->mpad, max_frames, sizeof(T));
+  const size_t smem = shape.smem;
   if (smem > 160 * 1024) return invalid_si("si_batch: filter support too long for the LDS tile");
   SiArgs<T> p;
   p.sig = d_signal;
@@ -192,13 +190,13 @@ static int32_t launch_si(const pds_si_plan *plan, const T *d_signal, const int64
   p.M = d.max_support;
   p.mpad = plan->mpad;
   p.C = d.num_coeffs;
-  p.JB = JB;
+  p.JB = shape.JB;
   p.use_power = d.use_power;
   p.use_log = d.use_log;
   p.log_floor = (T)d.log_floor;
   auto kern = d.taps_complex ? si_conv_kernel<T, true> : si_conv_kernel<T, false>;
   PDS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  dim3 grid((unsigned)((max_frames + JB - 2) / (JB - 1)), (unsigned)B);
+  dim3 grid(shape.grid_x, (unsigned)B);
   hipLaunchKernelGGL(kern, grid, dim3(kSiThreads), smem, (hipStream_t)stream, p);
   PDS_HIP(hipGetLastError());
   return PDS_OK;
@@ -237,8 +235,8 @@ int32_t pds_si_plan_create(const pds_si_desc *desc, const double *taps, const do
     plan = new pds_si_plan();
     plan->d = d;
     plan->device = device;
-    const int R = pds::kSiR, M = d.max_support, C = d.num_coeffs, w = d.taps_complex ? 2 : 1;
-    plan->mpad = (M + R - 1) / R * R;
+    const int M = d.max_support, C = d.num_coeffs, w = d.taps_complex ? 2 : 1;
+    plan->mpad = pds::si_mpad(M);
     std::vector<double> t64((size_t)C * plan->mpad * w, 0.0);
     for (int c = 0; c < C; ++c)
       for (int k = 0; k < M * w; ++k) t64[(size_t)c * plan->mpad * w + k] = taps[(size_t)c * M * w + k];
@@ -272,6 +270,25 @@ void pds_si_plan_destroy(pds_si_plan *plan) {
 int32_t pds_si_plan_fft_size(const pds_si_plan *plan) {
   if (!plan || plan->fft.blocks == 0) return 0;
   return plan->fft.big ? 2048 : 1024;
+}
+
+int32_t pds_si_launch_shape(const pds_si_plan *plan, int32_t B, int64_t max_frames, int32_t direct, int32_t *out) {
+  if (!plan) return pds::invalid_si("si_launch_shape: null plan");
+  if (!out) return pds::invalid_si("si_launch_shape: null out");
+  if (B < 1 || B > 65535 || max_frames < 1) return pds::invalid_si("si_launch_shape: need 1 <= B <= 65535, max_frames >= 1");
+  const pds_si_desc &d = plan->d;
+  if (direct || plan->fft.blocks == 0) {
+    // (the grid does not depend on the sample type; the LDS size does and is not reported)
+    const pds::SiDirectShape s = pds::si_direct_shape(d.frame_shift, plan->mpad, max_frames, sizeof(float));
+    const int32_t v[8] = {0, (int32_t)s.grid_x, 1, d.num_coeffs, s.JB, s.passes, s.JB - 1, plan->fft.num_cus};
+    std::copy(v, v + 8, out);
+  } else {
+    const pds::SiFftShape s = pds::si_fft_shape_of(plan, B, max_frames);
+    const int32_t v[8] = {s.NT, (int32_t)s.grid_x, (int32_t)s.groups, s.c_per_group, plan->fft.blocks, s.nw, s.per_wg,
+                          plan->fft.num_cus};
+    std::copy(v, v + 8, out);
+  }
+  return PDS_OK;
 }
 
 int64_t pds_si_scratch_len(const pds_si_plan *plan, int32_t B, int64_t max_frames) {

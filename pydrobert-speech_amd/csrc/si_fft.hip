@@ -27,6 +27,7 @@
 
 #include "fft_inlane.h"
 #include "pds_internal.h"
+#include "si_shape.h"
 
 // Phase boundaries of a filter's pass, as scheduling barriers (at one wave per SIMD they were worth 7 %;
 // at two waves -DPDS_SI_NO_PHASE measures +0.5 % on the 1024-point form and -2 % on the 2048-point one).
@@ -53,11 +54,13 @@ namespace pds {
 
 namespace {
 
-constexpr int kN = 1024, kL = 32;       // transform size; lanes = registers = 32
-constexpr int kRowStride = kL + 1;      // exchange row stride in float2: conflict-free both ways
-constexpr int kWaves = 8;               // wavefronts per workgroup (two per SIMD), two transforms each
+// (the sizes the launch shape depends on are si_shape.h's)
+constexpr int kN = kSiFftN, kL = kSiFftL;  // transform size; lanes = registers = 32
+constexpr int kRowStride = kSiFftRowStride;  // exchange row stride in float2: conflict-free both ways
+constexpr int kWaves = kSiFftWaves;     // wavefronts per workgroup (two per SIMD), two transforms each
 constexpr int kTwBatch = PDS_SI_TW_BATCH;   // twiddle rows read from LDS at a time
-constexpr int kMaxBlocks = 8;           // shift-sized blocks a transform may yield (register budget)
+constexpr int kMaxBlocks = kSiFftMaxBlocks;  // shift-sized blocks a transform may yield (register budget)
+constexpr int kMaxWindowRegs = kSiFftMaxWindowRegs;
 
 // x + (x of the lane a DPP control word selects inside the 16-lane row)
 template <int CTRL>
@@ -346,13 +349,13 @@ __global__ __launch_bounds__(kWaves * 64, 1) void si_fft_kernel(const SiFftArgs 
 }
 
 // frame t = first-half sum of block t + second-half sum of block t + 1 (compute.py:980-990)
-__global__ __launch_bounds__(256) void si_combine_kernel(const float *scratch, int64_t blocks_per_utt,
+__global__ __launch_bounds__(kSiCombineThreads) void si_combine_kernel(const float *scratch, int64_t blocks_per_utt,
                                                          const int64_t *nframes, const int64_t *row_off,
                                                          int C, int use_log, float log_floor, float *out,
                                                          int64_t out_stride) {
   const int b = blockIdx.y;
   const int64_t Tb = nframes[b];
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t e = (int64_t)blockIdx.x * kSiCombineThreads + threadIdx.x;
   if (e >= Tb * C) return;
   const int64_t t = e / C;
   const int c = (int)(e - t * C);
@@ -364,30 +367,15 @@ __global__ __launch_bounds__(256) void si_combine_kernel(const float *scratch, i
 
 }  // namespace
 
-// blocks of S filtered samples one NT-point transform yields for supports of M taps (0: none)
-constexpr int kMaxWindowRegs = 16;
-static int blocks_for(int NT, int M, int S) {
-  if (M > NT) return 0;
-  const int blocks = std::min(kMaxBlocks, (NT - (M - 1)) / S);
-  const int lanes = NT / kL;  // of one transform
-  if (blocks < 1 || S > kMaxWindowRegs * lanes) return 0;
-  // (the transposition area(s) of the transform -- 2.06 NT floats -- are reused for its NT squared
-  // samples; the block sums read less than `lanes` floats past them, weighted by zero)
-  return blocks;
-}
-
 int32_t si_fft_tables_create(pds_si_plan *plan, const double *taps) {
   SiFftTables &ft = plan->fft;
   ft.blocks = 0;
   const pds_si_desc &d = plan->d;
   const int M = d.max_support, S = d.frame_shift, C = d.num_coeffs;
-  // 1024- or 2048-point transforms: whichever spends less of a transform on the overlap (the
-  // larger one pays ~20 % more per point for its extra radix-2 stage)
-  const int b1 = blocks_for(kN, M, S), b2 = blocks_for(2 * kN, M, S);
-  const double eff1 = (double)b1 * S / kN, eff2 = (double)b2 * S / (2 * kN) / 1.2;
-  if (b1 == 0 && b2 == 0) return PDS_OK;  // supports too long for this form: direct kernel
-  ft.big = eff2 > eff1;
-  const int NT = ft.big ? 2 * kN : kN, blocks = ft.big ? b2 : b1;
+  const SiFftForm form = si_fft_form_for(M, S);  // 1024- or 2048-point transforms
+  if (form.blocks == 0) return PDS_OK;  // supports too long for this form: direct kernel
+  ft.big = form.big;
+  const int NT = ft.big ? 2 * kN : kN, blocks = form.blocks;
   std::vector<double> cs(NT), sn(NT);
   for (int j = 0; j < NT; ++j) {
     cs[j] = std::cos(2.0 * M_PI * j / NT);
@@ -432,13 +420,14 @@ void si_fft_tables_destroy(pds_si_plan *plan) {
   plan->fft = SiFftTables();
 }
 
-static int64_t transforms_for(const pds_si_plan *plan, int64_t max_frames) {
-  return (max_frames + 1 + plan->fft.blocks - 1) / plan->fft.blocks;
+SiFftShape si_fft_shape_of(const pds_si_plan *plan, int32_t B, int64_t max_frames) {
+  return si_fft_shape(plan->fft.big, plan->fft.blocks, plan->d.frame_shift, plan->d.num_coeffs, B, max_frames,
+                      plan->fft.num_cus);
 }
 
 int64_t si_fft_scratch_len(const pds_si_plan *plan, int32_t B, int64_t max_frames) {
   if (!plan || plan->fft.blocks == 0 || B <= 0 || max_frames <= 0) return 0;
-  return (int64_t)B * transforms_for(plan, max_frames) * plan->fft.blocks * plan->d.num_coeffs * 2;
+  return si_fft_shape_of(plan, B, max_frames).scratch_len;
 }
 
 int32_t launch_si_fft(const pds_si_plan *plan, const float *d_signal, const int64_t *d_offsets,
@@ -446,14 +435,14 @@ int32_t launch_si_fft(const pds_si_plan *plan, const float *d_signal, const int6
                       int32_t B, int64_t max_frames, int64_t start, const int64_t *d_starts, float *d_scratch,
                       float *d_out, int64_t out_stride, void *stream) {
   const pds_si_desc &d = plan->d;
-  const int64_t transforms = transforms_for(plan, max_frames);
+  const SiFftShape shape = si_fft_shape_of(plan, B, max_frames);
   SiFftArgs p;
   p.sig = d_signal;
   p.offsets = d_offsets;
   p.lengths = d_lengths;
   p.nframes = d_nframes;
   p.scratch = d_scratch;
-  p.blocks_per_utt = transforms * plan->fft.blocks;
+  p.blocks_per_utt = shape.blocks_per_utt;
   p.spectra = plan->fft.d_spectra;
   p.twiddle = plan->fft.d_twiddle;
   p.twiddle2k = plan->fft.d_twiddle2k;
@@ -464,29 +453,22 @@ int32_t launch_si_fft(const pds_si_plan *plan, const float *d_signal, const int6
   p.C = d.num_coeffs;
   p.blocks = plan->fft.blocks;
   p.use_power = d.use_power;
-  const size_t smem = ((size_t)2 * kWaves * kL * kRowStride + (plan->fft.big ? 3 : 1) * kL * kL) * sizeof(float2);
-  const int lanes = plan->fft.big ? 64 : kL;
+  const size_t smem = shape.smem;
   // window factors per lane and half: the smallest of the built counts that covers a block
-  const int nw = (p.S + lanes - 1) / lanes;
+  const int nw = shape.nw;
   void (*kern)(const SiFftArgs);
   if (plan->fft.big)
-    kern = nw <= 3 ? si_fft_kernel<true, 3> : nw <= 5 ? si_fft_kernel<true, 5> : nw <= 8 ? si_fft_kernel<true, 8> : si_fft_kernel<true, kMaxWindowRegs>;
+    kern = nw == 3 ? si_fft_kernel<true, 3> : nw == 5 ? si_fft_kernel<true, 5> : nw == 8 ? si_fft_kernel<true, 8> : si_fft_kernel<true, kMaxWindowRegs>;
   else
-    kern = nw <= 3 ? si_fft_kernel<false, 3> : nw <= 5 ? si_fft_kernel<false, 5> : nw <= 8 ? si_fft_kernel<false, 8> : si_fft_kernel<false, kMaxWindowRegs>;
-  const int per_wg = plan->fft.big ? kWaves : 2 * kWaves;  // transforms per workgroup
+    kern = nw == 3 ? si_fft_kernel<false, 3> : nw == 5 ? si_fft_kernel<false, 5> : nw == 8 ? si_fft_kernel<false, 8> : si_fft_kernel<false, kMaxWindowRegs>;
   PDS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  // few workgroups (one utterance, a streaming call): the filters are dealt to several workgroups per stretch, each
-  // repeating the stretch's forward transform -- 1 / c_per_group more work for a pass of filters in parallel
-  const int64_t wgs = (transforms + per_wg - 1) / per_wg * B;
-  const int want = (int)std::min<int64_t>(8, std::max<int64_t>(1, 2 * plan->fft.num_cus / std::max<int64_t>(1, wgs)));
-  p.c_per_group = (p.C + want - 1) / want;
-  const unsigned groups = (unsigned)((p.C + p.c_per_group - 1) / p.c_per_group);
-  dim3 grid((unsigned)((transforms + per_wg - 1) / per_wg), (unsigned)B, groups);
+  // (few workgroups: the filters are dealt to several workgroups per stretch, si_shape.h)
+  p.c_per_group = shape.c_per_group;
+  dim3 grid(shape.grid_x, (unsigned)B, shape.groups);
   hipLaunchKernelGGL(kern, grid, dim3(kWaves * 64), smem, (hipStream_t)stream, p);
   PDS_HIP(hipGetLastError());
-  const int64_t items = max_frames * d.num_coeffs;
-  dim3 grid2((unsigned)((items + 255) / 256), (unsigned)B);
-  hipLaunchKernelGGL(si_combine_kernel, grid2, dim3(256), 0, (hipStream_t)stream, d_scratch,
+  dim3 grid2(shape.combine_x, (unsigned)B);
+  hipLaunchKernelGGL(si_combine_kernel, grid2, dim3(kSiCombineThreads), 0, (hipStream_t)stream, d_scratch,
                      p.blocks_per_utt, d_nframes, d_row_off, d.num_coeffs, d.use_log, (float)d.log_floor,
                      d_out, out_stride);
   PDS_HIP(hipGetLastError());

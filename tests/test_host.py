@@ -309,6 +309,9 @@ def test_new_entry_points_validate_arguments_without_a_device():
     rc = lib.pds_si_batch_f32(null, null, null, null, null, null, 1, 1, 0, null, null, 1, null)
     assert rc < 0 and b"null plan" in lib.pds_last_error()
     assert lib.pds_si_scratch_len(null, 4, 100) == 0 and lib.pds_si_plan_fft_size(null) == 0
+    shape = (ctypes.c_int32 * 8)()
+    rc = lib.pds_si_launch_shape(null, 4, 100, 0, shape)
+    assert rc == -1 and b"si_launch_shape: null plan" in lib.pds_last_error() and list(shape) == [0] * 8
     desc = _native.SiDesc(frame_shift=0, max_support=10, num_coeffs=1, taps_complex=0, use_power=1, use_log=1,
                           reserved=0, reserved2=0, log_floor=1e-5)
     handle = ctypes.c_void_p()
