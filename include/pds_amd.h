@@ -365,6 +365,20 @@ int32_t pds_multistream_assemble_pcm(int32_t chunk_format, int32_t work_format, 
                                      int64_t capacity, int32_t frame_length, const int64_t *d_meta,
                                      const int64_t *d_tile_prefix, int32_t n, int64_t total_tiles, void *d_work,
                                      double preemph, void *d_prev, void *stream);
+/* ... with a dither in front that runs on across ticks (StreamBatch(dither=...)): pds_multistream_assemble_pcm's
+ * arguments, then d_dither -- int64[n][2], per entry [0] the position p of the chunk's first sample in the stream's raw
+ * signal (samples received since its start or reset, dropped ones included) and [1] the utterance's 64-bit key -- and
+ * the dither coefficient (finite).  Chunk sample ci is first dithered as pds_dither dithers sample p + ci of the
+ * stream's whole raw signal under that key,
+ *   y[ci] = (T)((double)(T)x[ci] + dither * noise(key, p + ci)),
+ * and the work span (and, with preemph != 0, the pre-emphasis: work[j] = (T)((double)y[ci] - preemph * (double)y[ci - 1]),
+ * the reference's order) is made of y where pds_multistream_assemble_pcm takes x.  d_prev then holds dithered previous
+ * samples.  Carried samples are work values and pass untouched.  dither == 0 is pds_multistream_assemble_pcm itself. */
+int32_t pds_multistream_assemble_dither(int32_t chunk_format, int32_t work_format, const void *d_chunks, void *d_pool,
+                                        int64_t capacity, int32_t frame_length, const int64_t *d_meta,
+                                        const int64_t *d_tile_prefix, int32_t n, int64_t total_tiles, void *d_work,
+                                        double preemph, void *d_prev, const int64_t *d_dither, double dither,
+                                        void *stream);
 
 /* ---------------------------------------------------------------------------------
  * Delta features of batched streaming (StreamBatch(deltas=...)): statics + d_1 .. d_K of every stream, delayed by the
@@ -475,6 +489,21 @@ int32_t pds_dither_f32(const float *d_in, int64_t total, double coeff, uint64_t 
                        void *stream);
 int32_t pds_dither_f64(const double *d_in, int64_t total, double coeff, uint64_t seed,
                        double *d_out, void *stream);
+/* pds_dither_packed: pds_dither over every utterance of a packed buffer in one launch.  Utterance b is
+ *   d_in[d_offsets[b] .. + d_lengths[b]) and receives exactly what pds_dither gives it alone with seed d_keys[b]
+ *   (uint64[B], on the device): the generator's counter restarts at 0 at d_offsets[b], whatever its parity.  Sample t of
+ *   an utterance takes pair t >> 1 of its key, the cosine branch for even t and the sine branch for odd t.  B <= 65535
+ *   per call; max_len >= every length.  Only the utterances' spans of d_out are written.  _i16_f32 reads 16-bit PCM,
+ *   widens it at the load (exact) and writes float32; d_out != d_in there, and may equal d_in in the other two. */
+int32_t pds_dither_packed_f32(const float *d_in, const int64_t *d_offsets, const int64_t *d_lengths,
+                              const uint64_t *d_keys, int32_t B, int64_t max_len, double coeff,
+                              float *d_out, void *stream);
+int32_t pds_dither_packed_f64(const double *d_in, const int64_t *d_offsets, const int64_t *d_lengths,
+                              const uint64_t *d_keys, int32_t B, int64_t max_len, double coeff,
+                              double *d_out, void *stream);
+int32_t pds_dither_packed_i16_f32(const int16_t *d_in, const int64_t *d_offsets,
+                                  const int64_t *d_lengths, const uint64_t *d_keys, int32_t B,
+                                  int64_t max_len, double coeff, float *d_out, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * Deltas.apply (reference post.py:462-491): correlation along a "time" axis of a

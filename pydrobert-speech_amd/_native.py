@@ -133,6 +133,9 @@ SIGNATURES = {
     "pds_preemphasize_f64": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_double, c_void_p, c_void_p]),
     "pds_dither_f32": (c_int32, [c_void_p, c_int64, c_double, ctypes.c_uint64, c_void_p, c_void_p]),
     "pds_dither_f64": (c_int32, [c_void_p, c_int64, c_double, ctypes.c_uint64, c_void_p, c_void_p]),
+    "pds_dither_packed_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_double, c_void_p, c_void_p]),
+    "pds_dither_packed_f64": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_double, c_void_p, c_void_p]),
+    "pds_dither_packed_i16_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_double, c_void_p, c_void_p]),
     "pds_deltas_f32": (c_int32, _DELTAS_ARGS),
     "pds_deltas_f64": (c_int32, _DELTAS_ARGS),
     "pds_deltas_rows_f32": (
@@ -187,6 +190,9 @@ SIGNATURES = {
     "pds_multistream_assemble_pcm": (
         c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_void_p,
                   c_double, c_void_p, c_void_p]),
+    "pds_multistream_assemble_dither": (
+        c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_void_p,
+                  c_double, c_void_p, c_void_p, c_double, c_void_p]),
     "pds_multistream_deltas_f32": (
         c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
                   c_int64, c_void_p, c_void_p]),

@@ -158,14 +158,15 @@ class FeatureDirWriter:
             return through_feed
         host = np.concatenate(signals) if offsets[-1] else np.zeros(0, self.dtype)
         packed = torch.from_numpy(host).to("cuda")
-        if packed.dtype == torch.int16:
+        if packed.dtype == torch.int16 and not (self.pre and isinstance(self.pre[0], Dither)):
             packed = packed.to(torch.float32)  # (uploaded as PCM, widened on the device)
         fused = 0.0
         for k, pre in enumerate(self.pre):
             if isinstance(pre, Dither):
-                for b in range(len(signals)):  # per-utterance stream, as the reference seeds torch
-                    seg = packed[offsets[b] : offsets[b + 1]]
-                    seg.copy_(Dither(pre.coeff, seed=self.seed + first_index + b).apply(seg))
+                # per-utterance stream, as the reference seeds torch, and one launch for the batch (PCM that is still
+                # int16 is widened by the dither's own load)
+                seeds = [self.seed + first_index + b for b in range(len(signals))]
+                packed = pre.apply_packed(packed, offsets[:-1], lengths, seeds=seeds)
             elif k == len(self.pre) - 1 and getattr(self.computer, "fuses_preemphasis", False):
                 fused = pre.coeff  # rides along with the frame loads (STFT computers only)
             else:

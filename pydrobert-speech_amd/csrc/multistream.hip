@@ -20,6 +20,17 @@
 // previous sample (the chunk's last raw sample, or the old one under an empty chunk) to the other half.  Tiles and lanes
 // read the half the metadata names and write the other, so no block reads what another block of the launch writes.
 //
+// Dither across ticks (StreamBatch(dither=...)): multistream_assemble_dither_kernel, the PCM kernel with every chunk
+// sample dithered first -- pre.hip::dither_kernel's noise (dither_noise.h) for the sample's position in the stream's raw
+// signal under the utterance's key, both from a second metadata section int64[n][2] (position of the chunk's first
+// sample, key) -- and, with a pre-emphasis, pre-emphasised against its dithered predecessor (the reference's order:
+// dither, then pre-emphasis).  A tile works in two phases.  Phase 1: its lanes take the whole sample pairs that cover the
+// tile's chunk samples and the one predecessor a pre-emphasis needs, one Philox block, logarithm, square root and
+// sincospi per pair, and write the dithered values to LDS (at most MS_TILE + 2 of them).  Phase 2, after one barrier:
+// the PCM kernel's loop with chunk values and predecessors read from LDS.  The previous-sample pool holds dithered
+// samples: the lanes behind the tiles compute the noise of the chunk's last sample themselves.  Carried samples pass
+// untouched.
+//
 // Delta features across ticks (StreamBatch(deltas=...)): multistream_deltas_kernel, after the STFT launches of a tick.
 // Every stream of the tick is one entry of `meta` (int64[n][MD_FIELDS]).  Its virtual sequence is its `valid` history
 // rows (pool half h) followed by its `fresh` new static rows; the entry's output rows are rows first .. first + rows of
@@ -49,6 +60,7 @@
 // sequence's last row.  Work is dealt by element as for the deltas.  Values are loaded and stored, never computed with,
 // so NaN payloads and signed zeros pass.
 #include "pds_internal.h"
+#include "dither_noise.h"
 
 namespace pds {
 
@@ -202,6 +214,126 @@ static int32_t launch_assemble_pcm(const void *d_chunks, void *d_pool, int64_t c
     hipLaunchKernelGGL((multistream_assemble_pcm_kernel<C, T, false>), dim3((unsigned)blocks), dim3(MS_THREADS), 0,
                        (hipStream_t)stream, (const C *)d_chunks, (T *)d_pool, capacity, frame_length, d_meta,
                        d_tile_prefix, n, total_tiles, (T *)d_work, preemph, (T *)d_prev);
+  PDS_HIP(hipGetLastError());
+  return PDS_OK;
+}
+
+// One kernel per working type: the chunk's type (T itself or int16) and the pre-emphasis are launch-wide flags, not
+// template parameters, and the noise is computed at one place in the code -- beside a Philox block, a logarithm, a
+// square root and a sincospi in float64 the branches cost nothing, and each further copy of that arithmetic is some
+// 2.5 KB of device code (tests/test_resources.py bounds the library's).
+template <typename T>
+__global__ __launch_bounds__(MS_THREADS) void multistream_assemble_dither_kernel(
+    const void *__restrict__ chunks, int32_t i16, T *__restrict__ pool, int64_t capacity, int32_t L,
+    const int64_t *__restrict__ meta, const int64_t *__restrict__ tile_prefix, int32_t n, int64_t total_tiles,
+    T *__restrict__ work, double coeff, T *__restrict__ prev, const int64_t *__restrict__ dmeta, double dither) {
+  __shared__ T noisy[MS_TILE + 2];  // dithered chunk samples of the tile, by position in the raw signal from `base`
+  const bool pre = coeff != 0.0;
+  const int64_t tile = blockIdx.x;
+  // behind the tiles (with a pre-emphasis only): one lane per entry, the entry's new (dithered) previous sample
+  const bool lanes = tile >= total_tiles;
+  int64_t e;
+  if (lanes) {
+    e = (tile - total_tiles) * MS_THREADS + threadIdx.x;
+    if (e >= n) return;
+  } else {  // entry of this tile: the last e with tile_prefix[e] <= tile (entries without samples have no tile)
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (tile_prefix[mid] <= tile) lo = mid; else hi = mid;
+    }
+    e = lo;
+  }
+  const int64_t *m = meta + e * MS_FIELDS;
+  const int64_t s = m[MS_STREAM], len = m[MS_CHUNK_LEN], carry_len = m[MS_CARRY_LEN], new_carry = m[MS_NEW_CARRY];
+  const int64_t drop = m[MS_DROP], chunk_off = m[MS_CHUNK_OFF];
+  const int64_t avail = carry_len + len - drop;
+  const int64_t half = m[MS_HALF] & 1;
+  const bool seen = (m[MS_HALF] & MS_SEEN) != 0;
+  const int64_t pos = dmeta[2 * e];  // chunk sample ci is sample pos + ci of the stream's raw signal
+  const uint64_t key = (uint64_t)dmeta[2 * e + 1];
+  const int64_t ci_at = drop - carry_len;  // work sample j >= carry_len is chunk sample ci_at + j
+  const int64_t j0 = lanes ? 0 : (tile - tile_prefix[e]) * MS_TILE;
+  const int64_t j1 = j0 + MS_TILE < avail ? j0 + MS_TILE : avail;
+  // phase 1.  A tile dithers chunk samples [ca, cb): its own (at most MS_TILE) and, with a pre-emphasis, the one before
+  // them; the pairs that cover their positions start at the even position `base` and number at most MS_TILE / 2 + 2,
+  // dealt to the lanes in turn.  A lane behind the tiles dithers the chunk's last sample: one pair of its own
+  int64_t ca, cb;
+  if (lanes) {
+    ca = len - 1, cb = len;
+  } else {
+    const int64_t cfirst = ci_at + (j0 > carry_len ? j0 : carry_len);
+    ca = pre && cfirst > 0 ? cfirst - 1 : cfirst, cb = ci_at + j1;
+  }
+  const int64_t base = (pos + (ca > 0 ? ca : 0)) & ~(int64_t)1;
+  const int64_t npairs = cb > ca && cb > 0 ? ((pos + cb - 1) >> 1) - (base >> 1) + 1 : 0;
+  const int64_t mine = lanes ? 0 : threadIdx.x;  // this lane's first pair
+  for (int64_t p = mine; p < npairs; p += MS_THREADS) {
+    const int64_t c0 = base + 2 * p - pos, c1 = c0 + 1;  // the pair's chunk samples (either may lie outside [ca, cb))
+    const bool in0 = c0 >= ca && c0 < cb, in1 = c1 >= ca && c1 < cb;
+    T x0 = T(0), x1 = T(0);  // (the loads before the arithmetic; int16 is widened exactly)
+    if (i16) {
+      const int16_t *x = (const int16_t *)chunks + chunk_off;
+      if (in0) x0 = (T)x[c0];
+      if (in1) x1 = (T)x[c1];
+    } else {
+      const T *x = (const T *)chunks + chunk_off;
+      if (in0) x0 = x[c0];
+      if (in1) x1 = x[c1];
+    }
+    double even, odd;
+    dither_pair((base >> 1) + p, key, dither, even, odd);
+    const T y0 = dither_add<T>((double)x0, even), y1 = dither_add<T>((double)x1, odd);
+    if (lanes) {
+      prev[(1 - half) * capacity + s] = in0 ? y0 : y1;
+    } else {
+      if (in0) noisy[2 * p] = y0;
+      if (in1) noisy[2 * p + 1] = y1;
+    }
+  }
+  if (lanes) {  // (an empty chunk hands the old value on)
+    if (len <= 0) prev[(1 - half) * capacity + s] = prev[half * capacity + s];
+    return;
+  }
+  const T *carry_in = pool + (half * capacity + s) * (int64_t)L;
+  T *carry_out = pool + ((1 - half) * capacity + s) * (int64_t)L;
+  T *dst = work + m[MS_WORK_OFF];
+  const T before = pre ? prev[half * capacity + s] : T(0);  // the stream's previous (dithered) sample, if it has one
+  __syncthreads();
+  // phase 2: the PCM kernel's loop over the dithered values (not unrolled: beside phase 1 the loads' latency is nothing)
+  const int64_t at = pos - base;  // noisy[at + ci] is chunk sample ci
+#pragma unroll 1
+  for (int64_t j = j0 + threadIdx.x; j < j1; j += MS_THREADS) {
+    T v;
+    if (j < carry_len) {
+      v = carry_in[j];
+    } else {
+      const int64_t ci = ci_at + j;
+      v = noisy[at + ci];
+      // pre.hip::preemph_kernel's arithmetic over the dithered signal; a stream's first sample passes unchanged
+      if (pre && (ci > 0 || seen))
+        v = (T)__dsub_rn((double)v, __dmul_rn(coeff, (double)(ci > 0 ? noisy[at + ci - 1] : before)));
+    }
+    dst[j] = v;
+    if (j >= new_carry && j - new_carry < L) carry_out[j - new_carry] = v;
+  }
+}
+
+template <typename T>
+static int32_t launch_assemble_dither(const void *d_chunks, bool i16, void *d_pool, int64_t capacity,
+                                      int32_t frame_length, const int64_t *d_meta, const int64_t *d_tile_prefix,
+                                      int32_t n, int64_t total_tiles, void *d_work, double preemph, void *d_prev,
+                                      const int64_t *d_dither, double dither, void *stream) {
+  const bool pre = preemph != 0.0;
+  // (with a pre-emphasis every entry takes part, whether it has a tile or not)
+  const int64_t blocks = total_tiles + (pre ? ((int64_t)n + MS_THREADS - 1) / MS_THREADS : 0);
+  if (n == 0 || blocks == 0) return PDS_OK;
+  if (blocks > 0x7fffffff) return invalid_ms("multistream_assemble_dither: too many tiles in one call");
+  if (!d_pool || !d_meta || !d_tile_prefix || !d_work || !d_dither || (pre && !d_prev))
+    return invalid_ms("multistream_assemble_dither: null pointer");
+  hipLaunchKernelGGL(multistream_assemble_dither_kernel<T>, dim3((unsigned)blocks), dim3(MS_THREADS), 0,
+                     (hipStream_t)stream, d_chunks, (int32_t)i16, (T *)d_pool, capacity, frame_length, d_meta,
+                     d_tile_prefix, n, total_tiles, (T *)d_work, preemph, (T *)d_prev, d_dither, dither);
   PDS_HIP(hipGetLastError());
   return PDS_OK;
 }
@@ -461,6 +593,29 @@ int32_t pds_multistream_assemble_pcm(int32_t chunk_format, int32_t work_format, 
                 : (f64 ? pds::launch_assemble_pcm<double, double> : pds::launch_assemble_pcm<float, float>);
   return fn(d_chunks, d_pool, capacity, frame_length, d_meta, d_tile_prefix, n, total_tiles, d_work, preemph, d_prev,
             stream);
+}
+
+int32_t pds_multistream_assemble_dither(int32_t chunk_format, int32_t work_format, const void *d_chunks, void *d_pool,
+                                        int64_t capacity, int32_t frame_length, const int64_t *d_meta,
+                                        const int64_t *d_tile_prefix, int32_t n, int64_t total_tiles, void *d_work,
+                                        double preemph, void *d_prev, const int64_t *d_dither, double dither,
+                                        void *stream) {
+  if (!(dither == dither) || dither - dither != 0.0)
+    return pds::invalid_ms("multistream_assemble_dither: dither must be finite");
+  if (dither == 0.0)
+    return pds_multistream_assemble_pcm(chunk_format, work_format, d_chunks, d_pool, capacity, frame_length, d_meta,
+                                        d_tile_prefix, n, total_tiles, d_work, preemph, d_prev, stream);
+  if (work_format != PDS_SAMPLES_F32 && work_format != PDS_SAMPLES_F64)
+    return pds::invalid_ms("multistream_assemble_dither: work_format must be PDS_SAMPLES_F32 or PDS_SAMPLES_F64");
+  if (chunk_format != work_format && chunk_format != PDS_SAMPLES_I16)
+    return pds::invalid_ms("multistream_assemble_dither: chunk_format must be work_format or PDS_SAMPLES_I16");
+  if (n < 0 || total_tiles < 0 || capacity < 0 || frame_length <= 0)
+    return pds::invalid_ms("multistream_assemble_dither: bad size");
+  if (!(preemph == preemph) || preemph - preemph != 0.0)
+    return pds::invalid_ms("multistream_assemble_dither: preemph must be finite");
+  auto fn = work_format == PDS_SAMPLES_F64 ? pds::launch_assemble_dither<double> : pds::launch_assemble_dither<float>;
+  return fn(d_chunks, chunk_format == PDS_SAMPLES_I16, d_pool, capacity, frame_length, d_meta, d_tile_prefix, n,
+            total_tiles, d_work, preemph, d_prev, d_dither, dither, stream);
 }
 
 int32_t pds_multistream_deltas_f32(const float *d_statics, float *d_hist, int64_t capacity, int32_t hist_rows,

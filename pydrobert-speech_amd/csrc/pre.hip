@@ -3,6 +3,7 @@
 // back to the signal's type.  The STFT kernels can also apply pre-emphasis while loading frames
 // (pds_stft_batch_*'s `preemph` argument), which saves this pass over the signal.
 #include "pds_internal.h"
+#include "dither_noise.h"
 
 namespace pds {
 
@@ -29,23 +30,7 @@ __global__ __launch_bounds__(256) void preemph_kernel(const T *__restrict__ in,
   }
 }
 
-// Philox4x32-10 (Salmon et al., SC'11): counter = element block, key = seed
-__device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
-// out[i] = in[i] + coeff * N(0, 1); one thread per 2 samples (one Box-Muller pair from 53+53 bits)
+// out[i] = in[i] + coeff * N(0, 1); one thread per 2 samples (one Box-Muller pair from 53+53 bits, dither_noise.h)
 template <typename T>
 __global__ __launch_bounds__(256) void dither_kernel(const T *__restrict__ in, int64_t total,
                                                      double coeff, uint64_t seed,
@@ -53,17 +38,48 @@ __global__ __launch_bounds__(256) void dither_kernel(const T *__restrict__ in, i
   const int64_t pairs = (total + 1) / 2;
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < pairs;
        q += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), 0u, 0u};
-    philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    // two uniforms in (0, 1] and [0, 1)
-    const double u1 = ((double)(((uint64_t)c[0] << 21) ^ (c[1] >> 11)) + 1.0) * (1.0 / 9007199254740992.0);
-    const double u2 = (double)(((uint64_t)c[2] << 21) ^ (c[3] >> 11)) * (1.0 / 9007199254740992.0);
-    const double rad = sqrt(-2.0 * log(u1));
-    double s, co;
-    sincospi(2.0 * u2, &s, &co);
+    double even, odd;
+    dither_pair(q, seed, coeff, even, odd);
     const int64_t i = 2 * q;
-    out[i] = (T)((double)in[i] + coeff * rad * co);
-    if (i + 1 < total) out[i + 1] = (T)((double)in[i + 1] + coeff * rad * s);
+    out[i] = dither_add<T>((double)in[i], even);
+    if (i + 1 < total) out[i + 1] = dither_add<T>((double)in[i + 1], odd);
+  }
+}
+
+// packed utterances, one launch: utterance b (blockIdx.y) is in[offsets[b] .. + lengths[b]) and takes the noise of
+// dither_kernel over it alone under seed keys[b] -- pair q of the utterance is its samples 2q and 2q + 1, whatever the
+// parity of offsets[b]; the last sample of an odd length takes the cosine branch of its pair alone.  `i16`: `in` holds
+// 16-bit PCM, widened at the load, exactly (a launch-wide flag: a kernel of its own would be one more copy of the noise
+// arithmetic for the sake of one load)
+template <typename T>
+__global__ __launch_bounds__(256) void dither_packed_kernel(const void *__restrict__ in, int32_t i16,
+                                                            const int64_t *__restrict__ offsets,
+                                                            const int64_t *__restrict__ lengths,
+                                                            const uint64_t *__restrict__ keys, double coeff,
+                                                            T *__restrict__ out) {
+  const int b = blockIdx.y;
+  const int64_t n = lengths[b], off = offsets[b];
+  T *y = out + off;
+  const uint64_t key = keys[b];
+  const int64_t pairs = (n + 1) / 2;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < pairs;
+       q += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = 2 * q;
+    const bool both = i + 1 < n;
+    T x0, x1 = T(0);  // (the loads before the arithmetic)
+    if (i16) {
+      const int16_t *x = (const int16_t *)in + off;
+      x0 = (T)x[i];
+      if (both) x1 = (T)x[i + 1];
+    } else {
+      const T *x = (const T *)in + off;
+      x0 = x[i];
+      if (both) x1 = x[i + 1];
+    }
+    double even, odd;
+    dither_pair(q, key, coeff, even, odd);
+    y[i] = dither_add<T>((double)x0, even);
+    if (both) y[i + 1] = dither_add<T>((double)x1, odd);
   }
 }
 
@@ -96,6 +112,23 @@ static int32_t launch_dither(const T *d_in, int64_t total, double coeff, uint64_
   return PDS_OK;
 }
 
+template <typename T>
+static int32_t launch_dither_packed(const void *d_in, bool i16, const int64_t *d_off, const int64_t *d_len,
+                                    const uint64_t *d_keys, int32_t B, int64_t max_len, double coeff,
+                                    T *d_out, void *stream) {
+  if (B < 0 || max_len < 0) return invalid_pre("dither_packed: negative size");
+  if (B == 0 || max_len == 0) return PDS_OK;
+  if (B > 65535) return invalid_pre("dither_packed: B > 65535");
+  if (!d_in || !d_off || !d_len || !d_keys || !d_out) return invalid_pre("dither_packed: null pointer");
+  if (i16 && (const void *)d_out == d_in) return invalid_pre("dither_packed: int16 samples cannot be dithered in place");
+  int64_t blocks = ((max_len + 1) / 2 + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(dither_packed_kernel<T>, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0,
+                     (hipStream_t)stream, d_in, (int32_t)i16, d_off, d_len, d_keys, coeff, d_out);
+  PDS_HIP(hipGetLastError());
+  return PDS_OK;
+}
+
 }  // namespace pds
 
 extern "C" {
@@ -116,6 +149,25 @@ int32_t pds_dither_f32(const float *d_in, int64_t total, double coeff, uint64_t 
 int32_t pds_dither_f64(const double *d_in, int64_t total, double coeff, uint64_t seed,
                        double *d_out, void *stream) {
   return pds::launch_dither<double>(d_in, total, coeff, seed, d_out, stream);
+}
+
+int32_t pds_dither_packed_f32(const float *d_in, const int64_t *d_offsets, const int64_t *d_lengths,
+                              const uint64_t *d_keys, int32_t B, int64_t max_len, double coeff,
+                              float *d_out, void *stream) {
+  return pds::launch_dither_packed<float>(d_in, false, d_offsets, d_lengths, d_keys, B, max_len, coeff,
+                                          d_out, stream);
+}
+int32_t pds_dither_packed_f64(const double *d_in, const int64_t *d_offsets, const int64_t *d_lengths,
+                              const uint64_t *d_keys, int32_t B, int64_t max_len, double coeff,
+                              double *d_out, void *stream) {
+  return pds::launch_dither_packed<double>(d_in, false, d_offsets, d_lengths, d_keys, B, max_len, coeff,
+                                           d_out, stream);
+}
+int32_t pds_dither_packed_i16_f32(const int16_t *d_in, const int64_t *d_offsets,
+                                  const int64_t *d_lengths, const uint64_t *d_keys, int32_t B,
+                                  int64_t max_len, double coeff, float *d_out, void *stream) {
+  return pds::launch_dither_packed<float>(d_in, true, d_offsets, d_lengths, d_keys, B, max_len, coeff,
+                                          d_out, stream);
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@ samples of up to `capacity` streams in a device pool and takes every stream that
     sb = StreamBatch(computer, capacity=4096, preemphasis=0.97)   # Preemphasize(0.97) over every stream's whole signal
     sb = StreamBatch(computer, capacity=4096, cmvn=Standardize())  # running CMVN per stream, see below
     sb = StreamBatch(computer, capacity=4096, stack=Stack(3))      # every 3 rows of a stream side by side, see below
+    sb = StreamBatch(computer, capacity=4096, dither=Dither(1.0, seed=5))   # Dither over every stream's whole signal
 
 Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
 the same chunks: the same row counts, dtype and -- for float32 and float64 samples -- the same values bit for bit as
@@ -53,6 +54,18 @@ launch pre-emphasises every chunk sample as it enters the work buffer, against t
 for a chunk's first sample, the stream's last raw sample, which a third ping-pong pool of one sample per stream keeps
 across ticks (:attr:`StreamState.has_sample` says whether there is one).  A stream's first sample after its start or
 ``finalize`` passes unchanged.  The carries hold pre-emphasised samples, so ``finalize`` needs nothing more.
+
+With `dither` (a :class:`pre.Dither`) a stream's rows are those of the same calls over ``Dither(coeff,
+seed=s).apply(x)`` of its whole raw signal x converted to `dtype`, cut where the chunks were cut, bit for bit -- in
+front of the pre-emphasis, if there is one, as in the reference's chain.  The generator is counter-based: the noise of
+sample t depends on the utterance's key and t alone, so the assemble launch (``pds_multistream_assemble_dither``)
+dithers every chunk sample as it enters the work buffer, given where the chunk starts in the stream's raw signal.
+:class:`DitherState` keeps, per stream, the raw samples received this utterance (dropped ones too) and the utterance's
+seed and key, and numbers the utterances the batch begins, from 0: streams begin in tick order and within a tick in the
+order of `ids`, and the n-th utterance has seed ``dither_base + n`` (:attr:`StreamBatch.dither_base`: the ``Dither``'s
+seed, or a 63-bit value drawn at construction).  ``finalize`` ends the utterance; the stream's next chunk begins a new
+one with the next seed at position 0.  :func:`StreamBatch.dither_seeds` names the seeds of the current utterances.  The
+carries and the previous-sample pool hold dithered samples, so ``finalize`` needs nothing more.
 
 With `cmvn` (a :class:`post.Standardize`) every static row is standardised as it is produced, in one of the two forms
 of the reference's ``Standardize`` that do not need the whole utterance.  Per stream, with x_1, x_2, .. its static rows
@@ -105,10 +118,10 @@ from . import _native, config
 from .alias import alias_factory_subclass_from_arg
 from .compute import PackedLayout, ShortTimeFourierTransformFrameComputer
 from .post import Deltas, PostProcessor, Stack, Standardize
-from .pre import Preemphasize, PreProcessor
+from .pre import Dither, Preemphasize, PreProcessor, dither_keys
 
-__all__ = ["CmvnState", "DeltaState", "StackState", "StreamBatch", "StreamState", "streaming_cmvn",
-           "streaming_deltas", "streaming_preemphasis", "streaming_stack"]
+__all__ = ["CmvnState", "DeltaState", "DitherState", "StackState", "StreamBatch", "StreamState", "streaming_cmvn",
+           "streaming_deltas", "streaming_dither", "streaming_preemphasis", "streaming_stack"]
 
 _FIELDS = 8  # int64 per entry of pds_multistream_assemble's metadata (include/pds_amd.h)
 _DFIELDS = 8  # ... and of pds_multistream_deltas'
@@ -269,6 +282,88 @@ def streaming_preemphasis(preemphasis) -> float:
     if not np.isfinite(coeff):
         raise ValueError("StreamBatch: the pre-emphasis coefficient must be finite")
     return coeff
+
+
+def streaming_dither(dither) -> Optional[Tuple[float, Optional[int]]]:
+    """`dither` as :class:`StreamBatch` takes it -- a :class:`pre.Dither` or what
+    ``alias_factory_subclass_from_arg(PreProcessor, ...)`` makes one -> ``(coeff, seed)`` with `seed` the ``Dither``'s
+    own (None without one), or None for no dither (``None`` or a coefficient of 0); ``ValueError`` for anything else"""
+    if dither is None:
+        return None
+    if isinstance(dither, (bool, np.bool_, int, float, np.integer, np.floating)):
+        raise ValueError("StreamBatch: dither must be a pre.Dither (a bare number says nothing about the seed)")
+    try:
+        pre = alias_factory_subclass_from_arg(PreProcessor, dither)
+    except (KeyError, TypeError, ValueError) as e:
+        raise ValueError(f"StreamBatch: dither is no pre-processor ({e!r})") from None
+    if not isinstance(pre, Dither):
+        raise ValueError("StreamBatch: dither must be a pre.Dither")
+    coeff, seed = pre.coeff, pre.seed
+    if isinstance(coeff, (bool, np.bool_)) or not isinstance(coeff, (int, float, np.integer, np.floating)):
+        raise ValueError("StreamBatch: the dither coefficient must be a number")
+    coeff = float(coeff)
+    if not np.isfinite(coeff):
+        raise ValueError("StreamBatch: the dither coefficient must be finite")
+    if seed is not None:
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 63:
+            raise ValueError("StreamBatch: the dither seed must be an integer in [0, 2**63): the utterances' seeds "
+                             "count up from it")
+        seed = int(seed)
+    if coeff == 0.0:
+        return None
+    return coeff, seed
+
+
+class DitherState:
+    """Host bookkeeping of the dither of many streams.  Needs no device.
+
+    `base`: the seed of the first utterance the batch begins; ``count`` utterances begun so far, the next one has seed
+    ``base + count``.  Per stream: ``seed`` of its current utterance (-1: none begun), ``key`` its generator key
+    (:func:`pre.dither_keys`, the uint64's bits as int64) and ``pos`` raw samples received this utterance, dropped ones
+    included: the position of its next chunk's first sample.
+    """
+
+    def __init__(self, capacity: int, base: int):
+        capacity, base = int(capacity), int(base)
+        if capacity <= 0 or not 0 <= base < 1 << 63:
+            raise ValueError("capacity must be positive and the base seed lie in [0, 2**63)")
+        self.capacity, self.base, self.count = capacity, base, 0
+        self.seed = np.full(capacity, -1, dtype=np.int64)
+        self.key = np.zeros(capacity, dtype=np.int64)
+        self.pos = np.zeros(capacity, dtype=np.int64)
+
+    def step(self, ids: np.ndarray, lengths: np.ndarray) -> dict:
+        """What a tick that brings streams `ids` chunks of `lengths` does, without changing the state: the streams
+        without an utterance begin one, in the order of `ids`, with the next seeds; per stream the `seed` and `key` of
+        its utterance, the position `pos` of the chunk's first sample, and the state after the tick"""
+        lengths = np.asarray(lengths, dtype=np.int64)
+        seed, key = self.seed[ids], self.key[ids]  # (copies)
+        fresh = np.flatnonzero(seed < 0)
+        if len(fresh):
+            first = self.base + self.count
+            if first + len(fresh) > 1 << 63:
+                raise OverflowError("the dither seeds have run past 2**63")
+            seed[fresh] = first + np.arange(len(fresh), dtype=np.int64)
+            key[fresh] = dither_keys(seed[fresh].tolist()).view(np.int64)
+        pos = self.pos[ids]
+        return dict(seed=seed, key=key, pos=pos, next_pos=pos + lengths, next_count=self.count + len(fresh))
+
+    def commit(self, ids: np.ndarray, step: dict) -> None:
+        self.seed[ids] = step["seed"]
+        self.key[ids] = step["key"]
+        self.pos[ids] = step["next_pos"]
+        self.count = step["next_count"]
+
+    def reset(self, ids: np.ndarray) -> None:
+        """the streams' utterances are over (``finalize``): their next chunks begin new ones"""
+        self.seed[ids] = -1
+        self.key[ids] = 0
+        self.pos[ids] = 0
+
+    def fill_meta(self, meta: np.ndarray, step: dict) -> None:
+        """pds_multistream_assemble_dither's second metadata section of a tick into `meta` (int64[n, 2])"""
+        meta[:, 0] = step["pos"]
+        meta[:, 1] = step["key"]
 
 
 def streaming_deltas(deltas) -> Optional[Tuple[Deltas, int, int]]:
@@ -620,19 +715,21 @@ def _place(sections):
 
 
 @functools.lru_cache(maxsize=256)  # (a batch's ticks repeat a few sizes: each is placed once)
-def _tick_layout(n, E, launch_rows, chunks, deltas, cmvn, stack=False):
+def _tick_layout(n, E, launch_rows, chunks, deltas, cmvn, stack=False, dither=False):
     """The sections behind the samples in the upload of a tick over `n` streams of which `E` emit frames, placed: the
     assemble metadata and the tile prefix (`chunks`: a ``compute_chunks`` tick; ``finalize`` has neither, and no
     samples), the launch metadata -- `launch_rows` rows, one column per emitting stream --, the deltas metadata and
-    the element prefix (`deltas`), the cmvn metadata (`cmvn`), the stack metadata and its element prefix (`stack`)"""
-    # (a batch without `stack` has the layout it had before there was one: the two sections are not placed at all)
+    the element prefix (`deltas`), the cmvn metadata (`cmvn`), the stack metadata and its element prefix (`stack`), the
+    positions and keys of the dither (`dither`, in a ``compute_chunks`` tick)"""
+    # (a batch without `stack` / `dither` has the layout it had before there was one: their sections are not placed at all)
     return _place((("assemble", (n if chunks else 0, _FIELDS)),
                    ("tiles", (n + 1 if chunks else 0,)),
                    ("launch", (launch_rows, E)),
                    ("deltas", (n if deltas else 0, _DFIELDS)),
                    ("elems", (n + 1 if deltas else 0,)),
                    ("cmvn", (n if cmvn else 0, _CFIELDS)))
-                  + ((("stack", (n, _KFIELDS)), ("stack_elems", (n + 1,))) if stack else ()))
+                  + ((("stack", (n, _KFIELDS)), ("stack_elems", (n + 1,))) if stack else ())
+                  + ((("dither", (n if chunks else 0, 2)),) if dither else ()))
 
 
 class _TickBatch:
@@ -648,7 +745,7 @@ class _TickBatch:
     _launch_extra = ()
 
     def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None, cmvn=None,
-                 cmvn_running=True, stack=None):
+                 cmvn_running=True, stack=None, dither=None):
         # every argument is read before a device is touched
         if not isinstance(computer, self._computer_type):
             raise TypeError(self._wrong_computer)
@@ -658,6 +755,7 @@ class _TickBatch:
         spec, coeff = streaming_deltas(deltas), streaming_preemphasis(preemphasis)
         cspec = streaming_cmvn(cmvn, bool(cmvn_running), computer.num_coeffs)
         kspec = streaming_stack(stack)
+        nspec = streaming_dither(dither)
         self.state, row_length = self._new_state(computer, capacity)
         # the device side: `computer`'s plan, the carry pool of ``2 * capacity * row_length`` samples, the
         # previous-sample pool (with a pre-emphasis), the staging buffers, the history pool of the deltas, the pool of
@@ -682,6 +780,14 @@ class _TickBatch:
         self.preemphasis = coeff
         self._prev = torch.zeros((2, self.capacity), dtype=self._tdtype, device=self.device) if coeff else None
         self._format = _SAMPLES_F32 if dtype == np.float32 else _SAMPLES_F64
+        # the dither: host state only (the noise is a function of position and key; the device keeps nothing for it)
+        self.nstate = None
+        self.dither = 0.0
+        if nspec is not None:
+            self.dither, base = nspec
+            if base is None:
+                base = int(np.random.SeedSequence().generate_state(1, np.uint64)[0] >> 1)
+            self.nstate = DitherState(self.capacity, base)
         # pinned upload buffers (int64 words: samples, then metadata), used in turn; the event of a buffer's last
         # copy is waited for before it is written again
         self._up = [None, None]
@@ -732,6 +838,21 @@ class _TickBatch:
     def num_vectors(self) -> int:
         """rows of a stream side by side in a returned row (1 without `stack`)"""
         return self.kstate.nv if self.kstate is not None else 1
+
+    @property
+    def dither_base(self) -> Optional[int]:
+        """the seed of the first utterance this object began or will begin (None without `dither`): the ``Dither``'s
+        seed, or the 63-bit value drawn at construction when it had none"""
+        return self.nstate.base if self.nstate is not None else None
+
+    def dither_seeds(self, ids) -> np.ndarray:
+        """int64 per stream of `ids`: the seed of its current utterance -- ``Dither(coeff, seed=that).apply`` over the
+        utterance's whole raw signal gives the samples its features are made of --, -1 for a stream that has not
+        started"""
+        self._check_open()
+        if self.nstate is None:
+            raise ValueError(f"{type(self).__name__} was built without dither")
+        return self.nstate.seed[self.state.check_ids(ids)].copy()
 
     def started(self, ids) -> np.ndarray:
         """bool per stream of `ids`: between its first chunk and its ``finalize``"""
@@ -900,7 +1021,8 @@ class _TickBatch:
         row0 = rows[:-1]
         order = self._emit_order(step, np.flatnonzero(k > 0))
         up = _Upload(ns, _tick_layout(n, len(order), 4 + len(self._launch_extra), not final, self.dstate is not None,
-                                      self.cstate is not None, self.kstate is not None))
+                                      self.cstate is not None, self.kstate is not None,
+                                      *((True,) if self.nstate is not None else ())))
         slot, buf = self._staging(up.words)
         up.pinned = buf.numpy()
         if ns:
@@ -917,6 +1039,9 @@ class _TickBatch:
             am[:, 6] = off
             am[:, 7] = step["word"]
             up.host("tiles")[:] = tile_prefix
+            if self.nstate is not None:
+                nstep = self.nstate.step(ids, lengths)
+                self.nstate.fill_meta(up.host("dither"), nstep)
         lm = up.host("launch")
         lm[0], lm[1], lm[2], lm[3] = off[order], span[order], k[order], row0[order]
         for r, key in enumerate(self._launch_extra, 4):
@@ -942,12 +1067,18 @@ class _TickBatch:
         else:
             samples = up.dev("samples") if host_chunks is not None else d_samples
             signal = self._assemble_launch(samples if total else None, i16, up.dev("assemble"), up.dev("tiles"), n,
-                                           int(tile_prefix[-1]), int(work_off[-1]), stream)
+                                           int(tile_prefix[-1]), int(work_off[-1]), stream,
+                                           up.dev("dither") if self.nstate is not None else None)
         feats = self._feature_launch(signal, up.dev("launch"), order, step, off, span, rows, stream)
         if final:
             st.reset(ids)
         else:
             st.commit_chunks(ids, step)
+        if self.nstate is not None:
+            if final:
+                self.nstate.reset(ids)
+            else:
+                self.nstate.commit(ids, nstep)
         if self.cstate is not None:
             self._cmvn_launch(feats, up.dev("cmvn"), ids, cstep, stream)
         if self.dstate is not None:
@@ -956,13 +1087,20 @@ class _TickBatch:
             return self._stack_launch(feats, up.dev("stack"), up.dev("stack_elems"), ids, kstep, kelems, stream)
         return feats, rows
 
-    def _assemble_launch(self, samples, i16, d_meta, d_tile_prefix, n, tiles, work_len, stream):
+    def _assemble_launch(self, samples, i16, d_meta, d_tile_prefix, n, tiles, work_len, stream, d_dither=None):
         """one pds_multistream_assemble launch: the tick's work buffer (returned) and the new carries, in the other
-        pool half; `samples`: the device tensor the chunks start in (only its address is used; None: no samples)"""
+        pool half; `samples`: the device tensor the chunks start in (only its address is used; None: no samples);
+        `d_dither`: the positions and keys of a batch with `dither`"""
         torch = self._torch
         work = torch.empty(max(work_len, 1), dtype=self._tdtype, device=self.device)
         chunks = samples.data_ptr() if samples is not None else None
-        if i16 or self._prev is not None:
+        if d_dither is not None:
+            rc = self._lib.pds_multistream_assemble_dither(
+                _SAMPLES_I16 if i16 else self._format, self._format, chunks, self._pool.data_ptr(), self.capacity,
+                self._row_length, d_meta.data_ptr(), d_tile_prefix.data_ptr(), n, tiles, work.data_ptr(),
+                self.preemphasis, self._prev.data_ptr() if self._prev is not None else None, d_dither.data_ptr(),
+                self.dither, stream.cuda_stream)
+        elif i16 or self._prev is not None:
             rc = self._lib.pds_multistream_assemble_pcm(
                 _SAMPLES_I16 if i16 else self._format, self._format, chunks, self._pool.data_ptr(), self.capacity,
                 self._row_length, d_meta.data_ptr(), d_tile_prefix.data_ptr(), n, tiles, work.data_ptr(),
@@ -1075,8 +1213,19 @@ class StreamBatch(_TickBatch):
     pending rows, ``2 * capacity * (nv - 1) * C`` elements of `dtype`, and per tick the ``(new rows, C)`` rows before
     stacking.
 
+    `dither`: a :class:`pre.Dither` (or what ``alias_factory_subclass_from_arg(PreProcessor, ...)`` makes one:
+    ``"dither"``, ``{"name": "dither", "coeff": 1.0, "seed": 5}``); ``None`` or a coefficient of 0: none.  Every
+    stream's raw signal, converted to `dtype`, is dithered as ``Dither.apply`` does it over the whole signal, whatever
+    the cuts, before the pre-emphasis if there is one.  The batch numbers the utterances it begins from 0 -- streams
+    begin in tick order and within a tick in the order of `ids` --, and the n-th is dithered with seed
+    ``dither_base + n`` (:attr:`dither_base`: the ``Dither``'s seed, which must lie in ``[0, 2**63)``, or a 63-bit value
+    drawn at construction); ``finalize`` ends a stream's utterance, and its next chunk begins a new one.
+    :func:`dither_seeds` returns the seeds of the streams' current utterances, so
+    ``Dither(coeff, seed=sb.dither_seeds([i])[0]).apply(x)`` reproduces the samples offline.  The ``Dither`` itself is
+    not changed.  No additional device memory; a tick's upload grows by two words per stream.
+
     Under ``config.FLOAT64_ARITHMETIC == "float32"`` float64 samples are rounded to float32 once in the work buffer
-    (after a pre-emphasis, which works in float64) and the float32 features widened (within the float32 tolerance of
+    (after a dither and a pre-emphasis, which work in float64) and the float32 features widened (within the float32 tolerance of
     the computer's path, not bit for bit); a `cmvn` then works on the widened features.
     """
 

@@ -12,6 +12,7 @@
     sb = SiStreamBatch(computer, capacity=4096, deltas=Deltas(2), preemphasis=0.97)   # as for StreamBatch
     sb = SiStreamBatch(computer, capacity=4096, cmvn=Standardize(), cmvn_running=True)  # as for StreamBatch
     sb = SiStreamBatch(computer, capacity=4096, stack=Stack(3))                         # as for StreamBatch
+    sb = SiStreamBatch(computer, capacity=4096, dither=Dither(1.0, seed=5))             # as for StreamBatch
 
 Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
 the same chunks: the same row counts, dtype and -- for float32 and float64 samples alike -- the same values bit for
@@ -182,8 +183,9 @@ class SiStreamBatch(_TickBatch):
     """``compute_chunk`` / ``finalize`` of many streams of one short-integration computer, one tick per call
 
     `computer`: a :class:`si.ShortIntegrationFrameComputer` (its plan and configuration are used; its own streaming
-    state is not touched).  `capacity`, `dtype`, `deltas`, `preemphasis`, `cmvn`, `cmvn_running`, `stack` and every
-    method (``cmvn_stats`` among them): as :class:`multistream.StreamBatch` -- with `cmvn` the static rows are
+    state is not touched).  `capacity`, `dtype`, `deltas`, `preemphasis`, `cmvn`, `cmvn_running`, `stack`, `dither` and
+    every method (``cmvn_stats`` and ``dither_seeds`` among them): as :class:`multistream.StreamBatch` -- with `dither`
+    every stream's raw signal is dithered across ticks, before the pre-emphasis; with `cmvn` the static rows are
     standardised frame by frame, running or by fixed statistics, before the deltas are taken, and with `stack` the rows
     are stacked last.  Device memory: the carry pool, ``2 * capacity * row_length`` samples with
     ``row_length = max(max_support - 1, skip0) + 2 * frame_shift`` (:attr:`SiStreamState.row_length`), plus what

@@ -18,7 +18,7 @@ import numpy as np
 from . import _native
 from .alias import AliasedFactory
 
-__all__ = ["Dither", "PreProcessor", "Preemphasize"]
+__all__ = ["Dither", "PreProcessor", "Preemphasize", "dither_keys"]
 
 _AXIS_DEP_MSG = (
     "Specifying axis in preprocessor.apply is deprecated. "
@@ -57,10 +57,29 @@ def _finish(t, was_gpu, dtype, original, in_place):
     return res
 
 
+def _seed_state(seed: Optional[int]) -> int:
+    """the 64-bit state a ``Dither(seed=seed)`` starts from (fresh entropy for ``None``)"""
+    return int(np.random.SeedSequence(seed).generate_state(1, np.uint64)[0])
+
+
+def _next_key(state: int) -> int:
+    """one step of the state: the generator key of the next launch (and the state after it)"""
+    return (state * 6364136223846793005 + 1442695040888963407) % (1 << 64)
+
+
+def dither_keys(seeds) -> np.ndarray:
+    """uint64 per seed: the generator key of the first ``apply`` of ``Dither(seed=s)`` -- the one rule by which
+    ``Dither``, :func:`Dither.apply_packed` and the batched streaming (``StreamBatch(dither=...)``) turn a seed into a
+    key"""
+    return np.fromiter((_next_key(_seed_state(int(s))) for s in seeds), dtype=np.uint64, count=len(seeds))
+
+
 class Dither(PreProcessor):
     """Add Gaussian noise of standard deviation `coeff` (aliases ``dither``, ``dithering``)
 
-    `seed` makes the noise reproducible; each :func:`apply` advances it.
+    `seed` makes the noise reproducible; each :func:`apply` advances it.  The noise of sample t of a signal depends on
+    the launch's key and t alone (``csrc/dither_noise.h``), so a signal may be dithered in pieces:
+    :func:`apply_packed` does many utterances in one launch, ``StreamBatch(dither=...)`` a stream chunk by chunk.
     """
 
     aliases = {"dither", "dithering"}
@@ -68,7 +87,13 @@ class Dither(PreProcessor):
     def __init__(self, coeff: float = 1.0, seed: Optional[int] = None):
         super().__init__()
         self.coeff = coeff
-        self._seed = int(np.random.SeedSequence(seed).generate_state(1, np.uint64)[0])
+        self._given_seed = seed
+        self._seed = _seed_state(seed)
+
+    @property
+    def seed(self) -> Optional[int]:
+        """the `seed` this object was built with"""
+        return self._given_seed
 
     def apply(self, signal, axis: Optional[int] = None, in_place: bool = False):
         if axis is not None:
@@ -92,12 +117,62 @@ class Dither(PreProcessor):
         torch = _native.require_device()
         lib = _native.lib()
         fn = lib.pds_dither_f32 if src.dtype == torch.float32 else lib.pds_dither_f64
-        self._seed = (self._seed * 6364136223846793005 + 1442695040888963407) % (1 << 64)
+        self._seed = _next_key(self._seed)
         with torch.cuda.device(src.device):
             rc = fn(src.data_ptr(), src.numel(), float(self.coeff), self._seed, dst.data_ptr(),
                     torch.cuda.current_stream(src.device).cuda_stream)
         _native.check(rc, "pds_dither")
         return dst
+
+    def apply_packed(self, signal, offsets, lengths, seeds=None):
+        """Dither every utterance of a packed GPU buffer in one launch (see ``compute_packed``)
+
+        `signal`: a 1-D GPU tensor of float32, float64 or int16 (16-bit PCM is widened on the device, exactly, and
+        gives a float32 result); utterance b is ``signal[offsets[b] : offsets[b] + lengths[b]]``.  With `seeds`, one
+        integer per utterance, utterance b receives exactly what the first ``apply`` of ``Dither(self.coeff,
+        seed=seeds[b])`` gives it alone, and this object's own seed sequence is not touched.  With ``seeds=None`` the
+        result is that of ``self.apply`` called once per utterance, in order: the seed sequence advances
+        ``len(lengths)`` times.  Returns a new tensor of `signal`'s length.  For float input, samples outside every
+        utterance keep their values; for int16 input only the utterance spans are defined.
+        """
+        torch = _native.require_device()
+        lib = _native.lib()
+        if not getattr(signal, "is_cuda", False) or signal.dim() != 1:
+            raise ValueError("signal must be a 1-D GPU tensor")
+        if signal.dtype not in (torch.float32, torch.float64, torch.int16):
+            raise ValueError("signal must be float32, float64 or int16")
+        offs_h = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        lens_h = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        B = len(lens_h)
+        if len(offs_h) != B:
+            raise ValueError("one offset per length")
+        if B and (offs_h.min() < 0 or lens_h.min() < 0 or int((offs_h + lens_h).max()) > signal.numel()):
+            raise ValueError("the utterances lie outside signal")
+        if seeds is None:
+            keys = np.empty(B, dtype=np.uint64)
+            for b in range(B):
+                self._seed = keys[b] = _next_key(self._seed)
+        else:
+            if len(seeds) != B:
+                raise ValueError("one seed per utterance")
+            keys = dither_keys(seeds)
+        signal = signal.contiguous()
+        if signal.dtype == torch.int16:
+            fn = lib.pds_dither_packed_i16_f32
+            out = torch.empty(signal.shape, dtype=torch.float32, device=signal.device)
+        else:
+            fn = lib.pds_dither_packed_f32 if signal.dtype == torch.float32 else lib.pds_dither_packed_f64
+            out = signal.clone()  # gaps between utterances keep their contents
+        # offsets, lengths and keys go up in one copy (a key's bits travel as int64)
+        table = torch.as_tensor(np.stack([offs_h, lens_h, keys.view(np.int64)])).to(signal.device)
+        with torch.cuda.device(signal.device):
+            for lo in range(0, B, 65535):
+                hi = min(B, lo + 65535)
+                rc = fn(signal.data_ptr(), table[0, lo:].data_ptr(), table[1, lo:].data_ptr(),
+                        table[2, lo:].data_ptr(), hi - lo, int(lens_h[lo:hi].max()), float(self.coeff),
+                        out.data_ptr(), torch.cuda.current_stream(signal.device).cuda_stream)
+                _native.check(rc, "pds_dither_packed")
+        return out
 
 
 class Preemphasize(PreProcessor):

@@ -2,7 +2,8 @@
 """Per-tick wall time of batched streaming (multistream.StreamBatch) against a loop of single-stream compute_chunk calls.
 
     python tools/stream_rate.py [--streams 64,1024,8192] [--ticks 200] [--loop 64,256] [--deltas] [--cmvn]
-                                [--stack N] [--samples {f32,i16}] [--preemph C] [--si] > profiles/<tag>_stream_rate.txt
+                                [--stack N] [--dither] [--samples {f32,i16}] [--preemph C] [--si]
+                                > profiles/<tag>_stream_rate.txt
 
 Configuration c1_readme_fbank of tests/golden/configs.json (16 kHz, 25 ms frames, 10 ms shift), 160-sample (10 ms)
 float32 chunks.  Per stream count S: `ticks` timed ticks after 20 untimed ones, each ending in a synchronisation --
@@ -15,7 +16,11 @@ variance normalisation per stream (rows "host+c" / "packed+c": one more launch p
 loop.  --stack N: the same ticks once more through StreamBatch(stack=Stack(N)), every N rows of a stream side by side
 (rows "host+s" / "packed+s": one more launch per tick, the same download in a third of the rows for N = 3; a tick
 returns a row every N-th time per stream, so "frames/tick" counts stacked rows), with --deltas also on top of the deltas
-(rows "host+d+s" / "packed+d+s"), and no loop.  --samples i16: the chunks are 16-bit PCM, int16 arrays on the host (two bytes per sample over
+(rows "host+d+s" / "packed+d+s"), and no loop.  --dither: the same ticks once more through
+StreamBatch(dither=Dither(1.0, seed=0)), every chunk sample dithered in the assemble launch (rows "host+n" / "packed+n":
+no launch more, two more int64 words per stream in the upload, one Philox block, logarithm, square root and sincospi in
+float64 per two samples), then the plain ticks a second time (rows "host again" / "packed again": the run's own
+run-to-run spread, beside which the difference is reported), and no loop.  --samples i16: the chunks are 16-bit PCM, int16 arrays on the host (two bytes per sample over
 the link) and an int16 tensor on the GPU; --preemph C: StreamBatch(preemphasis=C), the pre-emphasis carried across
 ticks in the assemble launch.  Either leaves the loop out (a single-stream compute_chunk has no counterpart to them).
 
@@ -50,6 +55,8 @@ def main():
     ap.add_argument("--cmvn", action="store_true", help="also time the ticks with cmvn=Standardize(); skips the loop")
     ap.add_argument("--stack", type=int, default=0, metavar="N",
                     help="also time the ticks with stack=Stack(N), alone and on top of --deltas; skips the loop")
+    ap.add_argument("--dither", action="store_true",
+                    help="also time the ticks with dither=Dither(1.0, seed=0), and the plain ticks twice; skips the loop")
     ap.add_argument("--samples", choices=("f32", "i16"), default="f32", help="sample type of the chunks")
     ap.add_argument("--preemph", type=float, default=0.0, metavar="C", help="pre-emphasis coefficient (0: none)")
     ap.add_argument("--si", action="store_true", help="short-integration streams (SiStreamBatch, s1_gabor_mel)")
@@ -65,6 +72,7 @@ def main():
     from pydrobert_speech_amd.multistream import StreamBatch
     from pydrobert_speech_amd.multistream_si import SiStreamBatch
     from pydrobert_speech_amd.post import Deltas, Stack, Standardize
+    from pydrobert_speech_amd.pre import Dither
 
     name = "s1_gabor_mel" if args.si else "c1_readme_fbank"
     Batch = SiStreamBatch if args.si else StreamBatch
@@ -86,7 +94,7 @@ def main():
         variant = f", {args.samples} samples" + (f", preemphasis {args.preemph:g}" if args.preemph else "")
         extra = dict(preemphasis=args.preemph)
     print(f"# {results['device']}, {name}, {n}-sample chunks ({chunk_ms:.0f} ms), {args.ticks} ticks{variant}")
-    print(f"{'streams':>8} {'api':>10} {'p50 ms':>8} {'p99 ms':>8} {'x real time':>12} {'frames/tick':>11}")
+    print(f"{'streams':>8} {'api':>12} {'p50 ms':>8} {'p99 ms':>8} {'x real time':>12} {'frames/tick':>11}")
     for S in [int(s) for s in args.streams.split(",")]:
         comp = computer()
         block = (3000 * rng.standard_normal((S, n))).astype(np.float32)
@@ -100,11 +108,15 @@ def main():
         apis += ("host+c", "packed+c") if args.cmvn else ()
         if args.stack > 1:
             apis += ("host+s", "packed+s") + (("host+d+s", "packed+d+s") if args.deltas else ())
+        if args.dither:
+            apis += ("host+n", "packed+n", "host again", "packed again")
         for api in apis:
-            stages = api.split("+")[1:]
+            stages = api.split(" ")[0].split("+")[1:]
             post = dict(deltas=Deltas(2)) if "d" in stages else dict(cmvn=Standardize()) if "c" in stages else {}
             if "s" in stages:
                 post["stack"] = Stack(args.stack)
+            if "n" in stages:
+                post["dither"] = Dither(1.0, seed=0)
             sb = Batch(comp, capacity=S, **post, **extra)
             times, frames = [], 0
             for t in range(warm + args.ticks):
@@ -123,9 +135,14 @@ def main():
             sb.close()
             p50, p99 = pct(times, 50), pct(times, 99)
             results[f"{api}_{S}"] = dict(p50_ms=p50, p99_ms=p99, realtime_x=chunk_ms / p50, frames_per_tick=frames / args.ticks)
-            print(f"{S:>8} {api:>10} {p50:>8.3f} {p99:>8.3f} {chunk_ms / p50:>12.1f} {frames / args.ticks:>11.1f}")
+            print(f"{S:>8} {api:>12} {p50:>8.3f} {p99:>8.3f} {chunk_ms / p50:>12.1f} {frames / args.ticks:>11.1f}")
+        if args.dither:
+            for api in ("host", "packed"):
+                a, b, d = (results[f"{k}_{S}"]["p50_ms"] for k in (api, api + " again", api + "+n"))
+                print(f"# {S} streams, {api}: dither {d - min(a, b):+.3f} ms on the plain tick "
+                      f"({min(a, b):.3f} -> {d:.3f}); the plain tick twice in this run: {a:.3f} / {b:.3f}")
     loops = [int(s) for s in args.loop.split(",") if s.strip() and int(s) > 0]  # (--loop 0: none)
-    for S in [] if args.deltas or args.cmvn or args.stack > 1 or variant else loops:
+    for S in [] if args.deltas or args.cmvn or args.stack > 1 or args.dither or variant else loops:
         comps = [computer() for _ in range(S)]
         block = (3000 * rng.standard_normal((S, n))).astype(np.float32)
         times = []
@@ -138,7 +155,7 @@ def main():
                 times.append(t1 - t0)
         p50, p99 = pct(times, 50), pct(times, 99)
         results[f"loop_{S}"] = dict(p50_ms=p50, p99_ms=p99, realtime_x=chunk_ms / p50)
-        print(f"{S:>8} {'loop':>10} {p50:>8.3f} {p99:>8.3f} {chunk_ms / p50:>12.1f}")
+        print(f"{S:>8} {'loop':>12} {p50:>8.3f} {p99:>8.3f} {chunk_ms / p50:>12.1f}")
         if f"host_{S}" in results or S == 256:
             per_stream = p50 / S
             print(f"#   loop: {1e3 * per_stream:.1f} us per compute_chunk call")
