@@ -549,6 +549,21 @@ int32_t pds_stack_rows_f32(const float *d_in, int64_t in_stride, const int64_t *
                            int64_t max_out_rows, int32_t coeff, int32_t num_vectors,
                            int32_t pad_mode, float *d_out, int64_t out_stride, void *stream);
 
+/* Cepstra (post.py Cepstra: DCT-II and lifter as one host-built float64 matrix) over R rows:
+ *   out[r, :copy_cols]     = in[r, :copy_cols]                       (the energy column, unchanged)
+ *   out[r, copy_cols + k]  = sum over f of M[k][f] * in[r, copy_cols + f],   k < K, f < F
+ * accumulated in float64 from +0.0 with f ascending, multiply and add rounded separately, rounded once
+ * to the rows' type.  d_matrix: K x F float64, row-major.  Strides in elements, at least the row widths
+ * (copy_cols + F in, copy_cols + K out); every offset is formed in 64 bits.  copy_cols + F <= 256, K <= 2^20.
+ * R == 0 returns PDS_OK without looking at the pointers; bad sizes, strides and null pointers return
+ * PDS_ERR_INVALID ("cepstra_rows: ...") before any HIP call. */
+int32_t pds_cepstra_rows_f32(const float *d_in, int64_t in_stride, int64_t R, int32_t F,
+                             const double *d_matrix /* [K][F] */, int32_t K, int32_t copy_cols,
+                             float *d_out, int64_t out_stride, void *stream);
+int32_t pds_cepstra_rows_f64(const double *d_in, int64_t in_stride, int64_t R, int32_t F,
+                             const double *d_matrix /* [K][F] */, int32_t K, int32_t copy_cols,
+                             double *d_out, int64_t out_stride, void *stream);
+
 /* ---------------------------------------------------------------------------------
  * Standardize / CMVN (reference post.py:193-212 accumulate, 250-295 apply) on a tensor
  * viewed as [outer, coeff, inner]; statistics are over outer x inner per coefficient.

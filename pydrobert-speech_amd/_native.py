@@ -148,6 +148,10 @@ SIGNATURES = {
         [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32,
          c_int32, c_void_p, c_int64, c_void_p],
     ),
+    "pds_cepstra_rows_f32": (
+        c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
+    "pds_cepstra_rows_f64": (
+        c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
     "pds_si_plan_create": (c_int32, [POINTER(SiDesc), c_void_p, c_void_p, POINTER(c_void_p)]),
     "pds_si_plan_destroy": (None, [c_void_p]),
     "pds_si_scratch_len": (c_int64, [c_void_p, c_int32, c_int64]),

@@ -16,7 +16,8 @@ Same command line and on-disk result as the reference's tool -- a text map of
 * a batch of utterances (``--batch-utts`` / ``--batch-samples``) is packed into one device
   buffer and goes through ONE launch per stage: dither, pre-emphasis (fused into the frame
   loader when it is the last pre-processor), the fused STFT/filter-bank kernel, then each
-  post-processor over the packed rows;
+  post-processor over the packed rows (a ``Cepstra`` -- ``--postprocess '[{"name": "mfcc", "num_ceps": 13}]'`` --
+  works row by row, so the whole batch is one call and one launch, and the row offsets stay as they are);
 * features come back in one transfer per batch and are written with ``torch.save``.
 
 Differences from the reference, by design: arithmetic is float32 unless ``--precision
@@ -37,7 +38,7 @@ import numpy as np
 
 from .alias import alias_factory_subclass_from_arg
 from .compute import FrameComputer
-from .post import Deltas, PostProcessor, Stack, Standardize
+from .post import Cepstra, Deltas, PostProcessor, Stack, Standardize
 from .pre import Dither, Preemphasize, PreProcessor
 from .util import SIGNAL_SOURCES, read_signal
 
@@ -240,6 +241,9 @@ class FeatureDirWriter:
                     continue
                 except ValueError:
                     pass  # a pad mode the row kernel does not have: per utterance below
+            elif isinstance(post, Cepstra):
+                feats = post.apply(feats, axis=-1)  # row by row: the whole packed batch in one launch, same rows
+                continue
             elif isinstance(post, Standardize) and post.have_stats:
                 feats = post.apply(feats, axis=-1)  # one global transform: the whole batch at once
                 continue

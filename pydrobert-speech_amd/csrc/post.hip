@@ -1,6 +1,7 @@
 // Post-processor kernels: Deltas (reference post.py:462-491) and Standardize / CMVN
 // (post.py:193-212, 250-295).  Both are streaming, HBM-bound element-wise/stencil work;
-// accumulation is float64 as in the reference.
+// accumulation is float64 as in the reference.  Cepstra (a DCT-II and lifter as one matrix; not in the
+// reference) is bound by its separately rounded float64 products and sums.
 #include "pds_internal.h"
 
 namespace pds {
@@ -526,9 +527,112 @@ int32_t launch_cmvn_rows_partials(const float *d_in, int64_t in_stride, const in
   return PDS_OK;
 }
 
+// ------------------------------------------------------------------ Cepstra ---------
+
+// Cepstra (post.py Cepstra: a DCT-II with the lifter folded into the matrix) over rows of `copy + F` columns: the
+// first `copy` columns pass, output column copy + k is the sum over f of M[k][f] x[copy + f] -- float64, from +0.0, f
+// ascending, multiply and add rounded separately, rounded once to the rows' type.  ONE kernel serves float32 and
+// float64 rows (`is64`; the library's device code has no room for two).  A block owns `rb` <= 64 rows: it stages them
+// as float64 in LDS with coalesced loads, at an odd row pitch so that lane = row reads meet no bank conflict; wave w
+// then produces output columns w, w + 4, ..: the matrix elements are wave-uniform (scalar loads), a lane's row comes
+// out of LDS.
+constexpr int kCepstraWidth = 256;  // copy + F the kernel serves: 16 rows at the odd pitch 257 fill 32.9 KB of LDS
+
+__global__ __launch_bounds__(256) void cepstra_rows_kernel(
+    const void *__restrict__ in, int64_t in_stride, int64_t R, int W, int copy,
+    const double *__restrict__ M, int K, void *__restrict__ out, int64_t out_stride, int rb, int is64) {
+  extern __shared__ double ctile[];  // [rb][W | 1]
+  const int pitch = W | 1, F = W - copy;
+  __builtin_assume(F > 0);  // (checked by launch_cepstra; spares the kernel an empty-sum path)
+  const int64_t r0 = (int64_t)blockIdx.x * rb;
+  const int64_t left = R - r0;
+  const int rows = left < rb ? (int)left : rb;
+  // staged by 32-bit words, so that both row types share the loads (a float64 row is 2 W of them, copied as they
+  // are; a float32 word is widened on its way into the tile), four loads of a thread in flight
+  const int wd = W << is64;
+  const int64_t sw = in_stride << is64;
+  const uint32_t *src = (const uint32_t *)in + r0 * sw;
+  const int n = rows * wd;
+  // e / wd for e < 64 * 512 (the quotient is off an integer by >= 0.5 / 512, the product's error is < 1e-4)
+  const float inv_wd = __builtin_amdgcn_rcpf((float)wd);
+  for (int e0 = threadIdx.x; e0 < n; e0 += 4 * 256) {
+    uint32_t v[4];
+    int at[4];  // the word's place in the tile, in 32-bit words
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      // (past the end: the last word once more, to the same place -- no branch)
+      const unsigned e = min(e0 + u * 256, n - 1);
+      const unsigned lr = (unsigned)(((float)e + 0.5f) * inv_wd);
+      const unsigned c = e - lr * wd;
+      v[u] = src[lr * (uint64_t)sw + c];
+      at[u] = 2 * lr * pitch + (is64 ? c : 2 * c);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      // (no branch: a float64 row's word goes to its place twice)
+      const long long d = __double_as_longlong((double)__uint_as_float(v[u]));
+      ((uint32_t *)ctile)[at[u]] = is64 ? v[u] : (uint32_t)d;
+      ((uint32_t *)ctile)[at[u] + 1 - is64] = is64 ? v[u] : (uint32_t)(d >> 32);
+    }
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  if (lane >= rows) return;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const double *x = ctile + lane * pitch;
+  const int64_t o = (r0 + lane) * out_stride;
+  for (int k = wave; k < copy + K; k += 4) {
+    double acc = 0.0;
+    if (k < copy) {
+      acc = x[k];
+    } else {
+      const double *m = M + (unsigned)(k - copy) * (unsigned)F;  // (K F < 2^28: launch_cepstra)
+#pragma unroll 4
+      for (int f = 0; f < F; ++f) acc = __dadd_rn(acc, __dmul_rn(m[f], x[copy + f]));
+    }
+    if (is64)
+      ((double *)out)[o + k] = acc;
+    else
+      ((float *)out)[o + k] = (float)acc;
+  }
+}
+
+static int32_t launch_cepstra(const void *d_in, int64_t in_stride, int64_t R, int32_t F, const double *d_matrix,
+                              int32_t K, int32_t copy_cols, void *d_out, int64_t out_stride, int is64,
+                              void *stream) {
+  if (R < 0) return invalid_post("cepstra_rows: negative row count");
+  if (F < 1 || K < 1 || copy_cols < 0) return invalid_post("cepstra_rows: bad F / K / copy_cols");
+  const int64_t W = (int64_t)copy_cols + F;
+  if (W > kCepstraWidth) return invalid_post("cepstra_rows: rows wider than 256 columns");
+  if (K > (1 << 20)) return invalid_post("cepstra_rows: more than 2^20 matrix rows");
+  if (in_stride < W || out_stride < (int64_t)copy_cols + K)
+    return invalid_post("cepstra_rows: stride too small");
+  if (R == 0) return PDS_OK;
+  if (!d_in || !d_matrix || !d_out) return invalid_post("cepstra_rows: null pointer");
+  // rows per block: 64, fewer where the float64 tile would pass the 64 KB a block gets without asking for more
+  int rb = 64;
+  while ((size_t)rb * (W | 1) * sizeof(double) > 64 * 1024) rb >>= 1;
+  const int64_t blocks = (R + rb - 1) / rb;
+  if (blocks > 0x7fffffff) return invalid_post("cepstra_rows: too many rows");
+  hipLaunchKernelGGL(cepstra_rows_kernel, dim3((unsigned)blocks), dim3(256), (size_t)rb * (W | 1) * sizeof(double),
+                     (hipStream_t)stream, d_in, in_stride, R, (int)W, copy_cols, d_matrix, K, d_out, out_stride, rb,
+                     is64);
+  PDS_HIP(hipGetLastError());
+  return PDS_OK;
+}
+
 }  // namespace pds
 
 extern "C" {
+
+int32_t pds_cepstra_rows_f32(const float *d_in, int64_t in_stride, int64_t R, int32_t F, const double *d_matrix,
+                             int32_t K, int32_t copy_cols, float *d_out, int64_t out_stride, void *stream) {
+  return pds::launch_cepstra(d_in, in_stride, R, F, d_matrix, K, copy_cols, d_out, out_stride, 0, stream);
+}
+int32_t pds_cepstra_rows_f64(const double *d_in, int64_t in_stride, int64_t R, int32_t F, const double *d_matrix,
+                             int32_t K, int32_t copy_cols, double *d_out, int64_t out_stride, void *stream) {
+  return pds::launch_cepstra(d_in, in_stride, R, F, d_matrix, K, copy_cols, d_out, out_stride, 1, stream);
+}
 
 int32_t pds_deltas_f32(const float *d_in, int64_t outer, int64_t time, int64_t inner,
                        const double *d_filts, const int32_t *d_filt_off, int32_t K,

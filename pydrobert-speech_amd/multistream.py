@@ -15,6 +15,7 @@ samples of up to `capacity` streams in a device pool and takes every stream that
     sb = StreamBatch(computer, capacity=4096, cmvn=Standardize())  # running CMVN per stream, see below
     sb = StreamBatch(computer, capacity=4096, stack=Stack(3))      # every 3 rows of a stream side by side, see below
     sb = StreamBatch(computer, capacity=4096, dither=Dither(1.0, seed=5))   # Dither over every stream's whole signal
+    sb = StreamBatch(computer, capacity=4096, cepstra=Cepstra(13))  # cepstral coefficients of every row, see below
 
 Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
 the same chunks: the same row counts, dtype and -- for float32 and float64 samples -- the same values bit for bit as
@@ -34,7 +35,7 @@ Both kinds of tick, of this class and of :class:`multistream_si.SiStreamBatch`, 
 :func:`_TickBatch._tick`: the streams' spans (where each one's samples lie in what the feature launch reads), the
 upload -- laid out by :func:`_tick_layout` and addressed by section name through :class:`_Upload`, nowhere by hand --,
 the assemble launch (``compute_chunks`` only), the feature launch, the commit or reset of the host state, then the
-cmvn, the deltas and the stack launch.  A class adds what differs through four hooks: its host state, the order in
+cepstra, the cmvn, the deltas and the stack launch.  A class adds what differs through four hooks: its host state, the order in
 which the emitting streams launch, its extra rows of launch metadata, and the feature launch itself.  A new stage is
 one edit there.
 
@@ -66,6 +67,13 @@ order of `ids`, and the n-th utterance has seed ``dither_base + n`` (:attr:`Stre
 seed, or a 63-bit value drawn at construction).  ``finalize`` ends the utterance; the stream's next chunk begins a new
 one with the next seed at position 0.  :func:`StreamBatch.dither_seeds` names the seeds of the current utterances.  The
 carries and the previous-sample pool hold dithered samples, so ``finalize`` needs nothing more.
+
+With `cepstra` (a :class:`post.Cepstra`) every static row becomes its `num_ceps` cepstral coefficients -- the first
+post stage of a tick: one ``pds_cepstra_rows`` launch over the tick's static rows straight after the feature launch
+(none in a tick without rows), before `cmvn`, `deltas` and `stack`, which all see rows of the cepstral width.  A row
+depends on nothing but itself, so the stage has no state, no pool and no metadata, and the upload is laid out as without
+it.  A stream's rows are those of the offline chain over its whole utterance, ``stack(deltas(cmvn(cepstra(statics))))``
+with whichever stages are present, bit for bit.
 
 With `cmvn` (a :class:`post.Standardize`) every static row is standardised as it is produced, in one of the two forms
 of the reference's ``Standardize`` that do not need the whole utterance.  Per stream, with x_1, x_2, .. its static rows
@@ -117,11 +125,11 @@ import numpy as np
 from . import _native, config
 from .alias import alias_factory_subclass_from_arg
 from .compute import PackedLayout, ShortTimeFourierTransformFrameComputer
-from .post import Deltas, PostProcessor, Stack, Standardize
+from .post import Cepstra, Deltas, PostProcessor, Stack, Standardize
 from .pre import Dither, Preemphasize, PreProcessor, dither_keys
 
-__all__ = ["CmvnState", "DeltaState", "DitherState", "StackState", "StreamBatch", "StreamState", "streaming_cmvn",
-           "streaming_deltas", "streaming_dither", "streaming_preemphasis", "streaming_stack"]
+__all__ = ["CmvnState", "DeltaState", "DitherState", "StackState", "StreamBatch", "StreamState", "streaming_cepstra",
+           "streaming_cmvn", "streaming_deltas", "streaming_dither", "streaming_preemphasis", "streaming_stack"]
 
 _FIELDS = 8  # int64 per entry of pds_multistream_assemble's metadata (include/pds_amd.h)
 _DFIELDS = 8  # ... and of pds_multistream_deltas'
@@ -467,6 +475,21 @@ class DeltaState:
         return int(prefix[-1])
 
 
+def streaming_cepstra(cepstra) -> Optional[Cepstra]:
+    """`cepstra` as :class:`StreamBatch` takes it -- a :class:`post.Cepstra` or what
+    ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one (``"mfcc"``, ``{"name": "mfcc", "num_ceps": 13}``)
+    -> the ``Cepstra``, or None for ``cepstra=None``; ``ValueError`` for anything else"""
+    if cepstra is None:
+        return None
+    try:
+        cepstra = alias_factory_subclass_from_arg(PostProcessor, cepstra)
+    except (KeyError, TypeError) as e:
+        raise ValueError(f"StreamBatch: cepstra is no post-processor ({e!r})") from None
+    if not isinstance(cepstra, Cepstra):
+        raise ValueError("StreamBatch: cepstra must be a post.Cepstra")
+    return cepstra
+
+
 def streaming_cmvn(cmvn, running: bool, num_coeffs: int) -> Optional[Tuple[Standardize, Optional[np.ndarray], bool]]:
     """`cmvn` as :class:`StreamBatch` takes it -- a :class:`post.Standardize` or what
     ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one -> ``(Standardize, prior, norm_var)`` with `prior`
@@ -745,7 +768,7 @@ class _TickBatch:
     _launch_extra = ()
 
     def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None, cmvn=None,
-                 cmvn_running=True, stack=None, dither=None):
+                 cmvn_running=True, stack=None, dither=None, cepstra=None):
         # every argument is read before a device is touched
         if not isinstance(computer, self._computer_type):
             raise TypeError(self._wrong_computer)
@@ -753,7 +776,14 @@ class _TickBatch:
         if dtype not in (np.float32, np.float64):
             raise TypeError("StreamBatch: samples must be float32 or float64")
         spec, coeff = streaming_deltas(deltas), streaming_preemphasis(preemphasis)
-        cspec = streaming_cmvn(cmvn, bool(cmvn_running), computer.num_coeffs)
+        # the computer's own width, which the feature launch writes, and the width the post stages see: the cepstral
+        # one with `cepstra` (whose bounds on the width are checked here, where it is known)
+        pspec = streaming_cepstra(cepstra)
+        width = computer.num_coeffs
+        if pspec is not None:
+            pspec._split(width)
+            width = pspec.num_ceps
+        cspec = streaming_cmvn(cmvn, bool(cmvn_running), width)
         kspec = streaming_stack(stack)
         nspec = streaming_dither(dither)
         self.state, row_length = self._new_state(computer, capacity)
@@ -766,7 +796,9 @@ class _TickBatch:
         self.dtype = dtype
         self.capacity = self.state.capacity
         self.device = torch.device("cuda", torch.cuda.current_device())
-        self._F = computer.num_coeffs  # statics per row
+        self._F0 = computer.num_coeffs  # coefficients of the computer per row
+        self._cepstra = pspec
+        self._F = width  # statics per row, as the post stages see them
         self._C = self._F  # ... and coefficients per row before stacking
         self._comp = computer
         self._plan = computer._native_plan(self.device)
@@ -1079,6 +1111,8 @@ class _TickBatch:
                 self.nstate.reset(ids)
             else:
                 self.nstate.commit(ids, nstep)
+        if self._cepstra is not None:
+            feats = self._cepstra.apply(feats)  # one launch on `stream`, none without rows
         if self.cstate is not None:
             self._cmvn_launch(feats, up.dev("cmvn"), ids, cstep, stream)
         if self.dstate is not None:
@@ -1213,6 +1247,14 @@ class StreamBatch(_TickBatch):
     pending rows, ``2 * capacity * (nv - 1) * C`` elements of `dtype`, and per tick the ``(new rows, C)`` rows before
     stacking.
 
+    `cepstra`: a :class:`post.Cepstra` (or what ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one:
+    ``"mfcc"``, ``{"name": "mfcc", "num_ceps": 13}``); ``None``: none.  The first post stage: every static row becomes
+    ``cepstra.apply(row)``, `num_ceps` wide, and `cmvn`, `deltas` and `stack` work on those rows (``F`` above is then
+    `num_ceps`: the width of the cmvn statistics and of :func:`cmvn_stats`, of the deltas' history and of
+    ``num_coeffs``), so a stream's rows are ``stack(deltas(cmvn(cepstra(statics))))`` of the offline objects over its
+    whole utterance, bit for bit.  ``ValueError`` here if the computer's width does not admit `num_ceps`.  No state,
+    no additional device memory, no change of a tick's upload; one more launch per tick that has rows.
+
     `dither`: a :class:`pre.Dither` (or what ``alias_factory_subclass_from_arg(PreProcessor, ...)`` makes one:
     ``"dither"``, ``{"name": "dither", "coeff": 1.0, "seed": 5}``); ``None`` or a coefficient of 0: none.  Every
     stream's raw signal, converted to `dtype`, is dithered as ``Dither.apply`` does it over the whole signal, whatever
@@ -1252,7 +1294,7 @@ class StreamBatch(_TickBatch):
         f32_arith = self.dtype == np.float64 and config.FLOAT64_ARITHMETIC == "float32"
         if f32_arith:
             signal = signal.to(torch.float32)
-        feats = torch.empty((R, self._F), dtype=torch.float32 if f32_arith else self._tdtype, device=self.device)
+        feats = torch.empty((R, self._F0), dtype=torch.float32 if f32_arith else self._tdtype, device=self.device)
         if len(order):
             pads = cp[order]
             cuts = [0, *(np.flatnonzero(np.diff(pads)) + 1).tolist(), len(order)]

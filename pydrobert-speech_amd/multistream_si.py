@@ -183,8 +183,8 @@ class SiStreamBatch(_TickBatch):
     """``compute_chunk`` / ``finalize`` of many streams of one short-integration computer, one tick per call
 
     `computer`: a :class:`si.ShortIntegrationFrameComputer` (its plan and configuration are used; its own streaming
-    state is not touched).  `capacity`, `dtype`, `deltas`, `preemphasis`, `cmvn`, `cmvn_running`, `stack`, `dither` and
-    every method (``cmvn_stats`` and ``dither_seeds`` among them): as :class:`multistream.StreamBatch` -- with `dither`
+    state is not touched).  `capacity`, `dtype`, `deltas`, `preemphasis`, `cmvn`, `cmvn_running`, `stack`, `dither`, `cepstra`
+    and every method (``cmvn_stats`` and ``dither_seeds`` among them): as :class:`multistream.StreamBatch` -- with `dither`
     every stream's raw signal is dithered across ticks, before the pre-emphasis; with `cmvn` the static rows are
     standardised frame by frame, running or by fixed statistics, before the deltas are taken, and with `stack` the rows
     are stacked last.  Device memory: the carry pool, ``2 * capacity * row_length`` samples with
@@ -216,7 +216,7 @@ class SiStreamBatch(_TickBatch):
         lib = self._lib
         f64 = self.dtype == np.float64
         batch = lib.pds_si_batch_starts_f64 if f64 else lib.pds_si_batch_starts_f32
-        feats = torch.empty((int(rows[-1]), self._F), dtype=self._tdtype, device=self.device)
+        feats = torch.empty((int(rows[-1]), self._F0), dtype=self._tdtype, device=self.device)
         k = step["k"][order]
         E = len(k)
         for lo in range(0, E, _MAX_UTTS_PER_CALL):

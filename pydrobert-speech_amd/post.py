@@ -1,9 +1,12 @@
-"""Post-processors on the hot path: ``Deltas`` and ``Standardize`` / ``CMVN``.
+"""Post-processors on the hot path: ``Deltas``, ``Standardize`` / ``CMVN`` and ``Cepstra``.
 
 Same classes, aliases, arguments and error behaviour as the reference's (post.py:38-491);
 the element-wise and stencil arithmetic runs in HIP kernels (``csrc/post.hip``) -- there
 is no CPU path.  Host code only decides shapes, pads for the non-default ``pad_mode`` s,
 and finalises the ``O(num_coeffs)`` mean/scale vectors of CMVN.
+
+``Cepstra`` is not in the reference: the DCT-II and lifter that turn log filter-bank outputs into cepstral
+coefficients (MFCCs), one HIP kernel over the rows with the matrix built on the host in float64.
 
 ``Stack`` moves data only: views for a single tensor, one copy
 kernel for a packed ragged batch.  CMVN statistics files (``rfilename``, ``save``) go through
@@ -11,14 +14,14 @@ kernel for a packed ragged batch.  CMVN statistics files (``rfilename``, ``save`
 """
 import abc
 import warnings
-from typing import Callable, Optional, Union
+from typing import Callable, Optional, Tuple, Union
 
 import numpy as np
 
 from . import _native
 from .alias import AliasedFactory
 
-__all__ = ["CMVN", "Deltas", "PostProcessor", "Stack", "Standardize"]
+__all__ = ["CMVN", "Cepstra", "Deltas", "PostProcessor", "Stack", "Standardize"]
 
 
 class PostProcessor(AliasedFactory):
@@ -658,3 +661,131 @@ class Stack(PostProcessor):
                 )
                 _native.check(rc, "pds_stack_rows")
         return out, new_offsets
+
+
+# ------------------------------------------------------------------ Cepstra ----------
+
+_CEPSTRA_MAX_WIDTH = 256  # columns of an input row pds_cepstra_rows serves (include/pds_amd.h)
+
+
+class Cepstra(PostProcessor):
+    """Cepstral coefficients: a DCT-II over the coefficient axis, then a lifter (MFCCs of log-mel features)
+
+    `axis` of :func:`apply` is the *coefficient* axis, of width W; it becomes `num_ceps` wide, every other axis is
+    kept.  With ``F = W`` (``F = W - 1`` with `energy`) the transform is
+
+        D[k, f] = s_k cos(pi k (f + 0.5) / F),  s_0 = sqrt(1 / F), s_k = sqrt(2 / F)      (``norm="ortho"``)
+        D[k, f] = 2 cos(pi k (f + 0.5) / F)                                               (``norm=None``)
+
+    -- Kaldi's matrix and ``scipy.fft.dct(type=2, norm="ortho")``, or scipy's unnormalised form -- and row k is scaled
+    by ``1 + 0.5 Q sin(pi k / Q)`` with ``Q = lifter`` (Kaldi's formula; ``0`` or ``None``: no lifter).  Both are folded
+    into one float64 matrix ``M[k, f] = lift[k] D[k, f]`` on the host (:func:`matrix`), once per width and device.
+
+    `energy`: column 0 of the input is the energy of a computer built with ``include_energy=True``; it is copied to
+    column 0 of the output as it is, the transform runs over the other ``W - 1`` columns and output columns
+    ``1 .. num_ceps - 1`` are cepstra ``1 .. num_ceps - 1`` (Kaldi's ``--use-energy=true``: the energy in the place of
+    c0).
+
+    The arithmetic is fixed: per row and output k a float64 accumulator starts at ``+0.0`` and takes
+    ``acc = acc + M[k, f] * float64(x[f])`` for ``f = 0 .. F - 1`` in that order, product and sum rounded separately,
+    and is rounded once to the row's dtype.  float32 and float64 keep their dtype; anything else is computed and
+    returned as float64.
+    """
+
+    aliases = {"cepstra", "dct", "mfcc"}
+
+    def __init__(self, num_ceps: int = 13, lifter: Optional[float] = 22.0, norm: Optional[str] = "ortho",
+                 energy: bool = False):
+        if isinstance(num_ceps, (bool, np.bool_)) or not isinstance(num_ceps, (int, np.integer)) or num_ceps < 1:
+            raise ValueError(f"Expected num_ceps to be a positive integer, got {num_ceps!r}")
+        if norm is not None and norm != "ortho":
+            raise ValueError(f'norm must be "ortho" or None, got {norm!r}')
+        if lifter is None:
+            lifter = 0.0
+        if isinstance(lifter, (bool, np.bool_)) or not isinstance(lifter, (int, float, np.integer, np.floating)):
+            raise ValueError(f"lifter must be a number or None, got {lifter!r}")
+        lifter = float(lifter)
+        if not np.isfinite(lifter) or lifter < 0:
+            raise ValueError(f"lifter must be finite and not negative, got {lifter!r}")
+        self.num_ceps, self.lifter, self.norm, self.energy = int(num_ceps), lifter, norm, bool(energy)
+        self._device_matrix = {}  # (width, device) -> device float64 [K, F]
+
+    def table(self, F: int) -> np.ndarray:
+        """the float64 ``[num_ceps, F]`` matrix of an `F`-point transform: DCT-II rows scaled by the lifter"""
+        k = np.arange(self.num_ceps, dtype=np.float64)[:, None]
+        f = np.arange(F, dtype=np.float64)[None, :]
+        D = np.cos(np.pi * k * (f + 0.5) / F)
+        if self.norm == "ortho":
+            D *= np.sqrt(2.0 / F)
+            D[0] = np.sqrt(1.0 / F)  # (cos(0) = 1)
+        else:
+            D *= 2.0
+        if self.lifter:
+            D *= 1.0 + 0.5 * self.lifter * np.sin(np.pi * k / self.lifter)
+        return D
+
+    def _split(self, width: int) -> Tuple[int, int]:
+        """``(F, copy_cols)`` of input rows of `width` columns, or ``ValueError``: the width is only known at apply"""
+        width, copy = int(width), int(self.energy)
+        F = width - copy
+        if F < 1 or self.num_ceps > F:
+            raise ValueError(
+                f"Cepstra: num_ceps = {self.num_ceps} needs at least {self.num_ceps + copy} coefficients"
+                f"{' (the energy among them)' if copy else ''}, got {width}")
+        if width > _CEPSTRA_MAX_WIDTH:
+            raise ValueError(f"Cepstra: rows of {width} coefficients; at most {_CEPSTRA_MAX_WIDTH} are served")
+        return F, copy
+
+    def matrix(self, width: int) -> Tuple[np.ndarray, int]:
+        """``(M, copy_cols)`` for input rows of `width` columns, as pds_cepstra_rows takes them: the host float64
+        ``[K, F]`` matrix and the leading columns that pass unchanged -- the whole table and 0, or with `energy` rows
+        ``1 ..`` of the ``(width - 1)``-point table and 1.  ``ValueError`` unless ``1 <= num_ceps <= F`` and
+        ``width <= 256``"""
+        F, copy = self._split(width)
+        return np.ascontiguousarray(self.table(F)[copy:]), copy
+
+    def _matrix_on(self, width, device):
+        key = (int(width), str(device))
+        if key not in self._device_matrix:
+            M, copy = self.matrix(width)
+            torch = _native.require_device()
+            # (num_ceps = 1 with energy: nothing to transform, no matrix)
+            self._device_matrix[key] = (torch.from_numpy(M).to(device) if len(M) else None, len(M), copy)
+        return self._device_matrix[key]
+
+    def apply(self, features, axis: int = -1, in_place: bool = False):
+        # (`in_place` is accepted and ignored: the shape changes)
+        on_gpu = _is_gpu_tensor(features)
+        if not on_gpu:
+            features = np.asarray(features)
+        shape = tuple(features.shape)
+        if not shape:
+            raise ValueError("Cepstra: expected at least one dimension")
+        axis = axis % len(shape)
+        W = shape[axis]
+        self._split(W)  # (the width's errors come before any device work)
+        torch = _native.require_device()
+        if on_gpu:
+            t = features if features.dtype in (torch.float32, torch.float64) else features.to(torch.float64)
+        else:
+            t = _to_device(features if features.dtype in (np.float32, np.float64) else features.astype(np.float64))
+        d_matrix, K, copy = self._matrix_on(W, t.device)
+        rows = t.movedim(axis, -1)
+        lead = tuple(rows.shape[:-1])
+        # a matrix whose rows are contiguous goes as it is, whatever its row stride (a column slice of a wider
+        # tensor); anything else as a contiguous (rows, W) copy
+        if not (rows.dim() == 2 and rows.stride(1) == 1 and (rows.stride(0) >= W or rows.shape[0] <= 1)):
+            rows = rows.reshape(int(np.prod(lead, dtype=np.int64)), W).contiguous()
+        R = rows.shape[0]
+        out = torch.empty((R, copy + K), dtype=t.dtype, device=t.device)
+        if R and K:
+            lib = _native.lib()
+            fn = lib.pds_cepstra_rows_f32 if t.dtype == torch.float32 else lib.pds_cepstra_rows_f64
+            with torch.cuda.device(t.device):
+                rc = fn(rows.data_ptr(), rows.stride(0) if R > 1 else W, R, W - copy, d_matrix.data_ptr(), K, copy,
+                        out.data_ptr(), out.stride(0), _stream(torch, t))
+            _native.check(rc, "pds_cepstra_rows")
+        elif R:
+            out.copy_(rows[:, :copy])
+        out = out.reshape(lead + (copy + K,)).movedim(-1, axis)
+        return out if on_gpu else out.cpu().numpy()

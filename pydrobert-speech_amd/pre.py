@@ -95,6 +95,10 @@ class Dither(PreProcessor):
         """the `seed` this object was built with"""
         return self._given_seed
 
+    def __repr__(self) -> str:
+        # (what the object was built with and nothing of where it lies: a test id made of it is the same in every run)
+        return f"Dither(coeff={self.coeff!r}, seed={self._given_seed!r})"
+
     def apply(self, signal, axis: Optional[int] = None, in_place: bool = False):
         if axis is not None:
             warnings.warn(_AXIS_DEP_MSG, DeprecationWarning)
@@ -184,6 +188,9 @@ class Preemphasize(PreProcessor):
     def __init__(self, coeff: float = 0.97):
         super().__init__()
         self.coeff = coeff
+
+    def __repr__(self) -> str:
+        return f"Preemphasize(coeff={self.coeff!r})"
 
     def apply(self, signal, axis: Optional[int] = None, in_place: bool = False):
         if axis is not None:

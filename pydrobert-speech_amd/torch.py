@@ -10,7 +10,8 @@ extractors, and the kernels have no backward.
 * ``PyTorchSTFTFrameComputer.from_stft_frame_computer(computer)``
 * ``PyTorchSIFrameComputer.from_si_frame_computer(computer)``
 * ``PyTorchPreemphasize(coeff)`` / ``.from_preemphasize(p)``, ``PyTorchDither(coeff)`` / ``.from_dither(d)``
-* ``PyTorchPostProcessorWrapper.from_postprocessor(p)``
+* ``PyTorchPostProcessorWrapper.from_postprocessor(p)`` (``Deltas``, ``Standardize``, ``Stack``, ``Cepstra``: the coefficient
+  axis is the last one)
 """
 import torch
 
