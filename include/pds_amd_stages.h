@@ -1,0 +1,104 @@
+/* C ABI of libpds_amd_stages.so: stage kernels for gfx950 (AMD Instinct MI355X) that are not part of the fused STFT
+ * kernel's instantiation matrix.  libpds_amd.so's device code is held to a size bound that guards that matrix
+ * (DESIGN.md section 4.3); stages that stand alone are built into this second, small library, which has a size cap of
+ * its own (64 KiB of device code), its own version and its own error string.  It shares no state with libpds_amd.so
+ * and may be loaded with or without it.
+ *
+ * Conventions as in pds_amd.h: every pointer named d_* is device memory of the current HIP device; `stream` is a
+ * hipStream_t (NULL: the default stream); calls are asynchronous on it; a return value other than 0 leaves a message
+ * for the calling thread in the string the last-error call returns.  There is no CPU path. */
+#ifndef PDS_AMD_STAGES_H
+#define PDS_AMD_STAGES_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define PDS_STAGES_OK 0
+#define PDS_STAGES_ERR_INVALID -1 /* bad argument */
+#define PDS_STAGES_ERR_HIP -2     /* a HIP runtime call failed */
+
+/* 100 * major + minor of this library; independent of libpds_amd.so's */
+int32_t pds_stages_version(void);
+/* the calling thread's message of its last failed call into this library ("" before any) */
+const char *pds_stages_last_error(void);
+
+/* ---------------------------------------------------------------------------------
+ * Sliding-window cepstral mean (and variance) normalisation: Kaldi's apply-cmvn-sliding; post.SlidingCMVN.
+ *
+ * The definition.  For an utterance of T frames, frame t, W = cmn_window >= 1, min_window >= 1, the window [ws, we) is
+ *
+ *     center:      ws = t - W / 2;  we = ws + W            (integer division)
+ *     not center:  ws = t - W;      we = t + 1
+ *     if ws < 0:                 we -= ws;  ws = 0
+ *     if not center and we > t:  we = max(t + 1, min_window)
+ *     if we > T:                 ws -= we - T;  we = T;  ws = max(ws, 0)
+ *
+ * so that 0 <= ws <= t < we <= T, ws and we each move by 0 or 1 from one frame to the next, and the window holds at
+ * most max(W + 1, min_window) frames (the causal window is W + 1 frames wide once it is full, as Kaldi's).  Per
+ * coefficient, in float64, with x widened first and every operation rounded separately (division and square root
+ * correctly rounded), refresh >= 1:
+ *
+ *     t % refresh == 0:  s1 = s2 = 0;  for u = ws .. we - 1 in order:  s1 += x_u;  s2 += x_u * x_u
+ *     else:              if ws moved:  s1 -= x_old;  s2 -= x_old * x_old      (x_old: the frame that left)
+ *                        then, if we moved:  s1 += x_new;  s2 += x_new * x_new  (x_new: the frame that entered)
+ *     n = we - ws;  mean = s1 / n;  y = x_t - mean
+ *     norm_vars:  n == 1:  y = 0
+ *                 else:    var = s2 / n - mean * mean;  if !(var > 1e-10) then var = 1e-10;  y = y * (1 / sqrt(var))
+ *
+ * and y is rounded once to the input's type.  `refresh` is part of the result (in its last bits): segments of
+ * `refresh` frames are independent, rounding does not drift over a long stream, and a NaN or infinite frame stops
+ * affecting the output at the first refresh after it has left the window.
+ *
+ * The offline call, over a packed ragged batch: utterance b is the d_nrows[b] rows from row d_row_off[b] on, of C
+ * values each, rows in_stride elements apart in d_in and out_stride apart in d_out (both >= C; row indices are the
+ * same in both).  One lane handles one (utterance, segment, coefficient), adjacent lanes adjacent coefficients;
+ * max_rows is the largest d_nrows[b] (it sizes the grid; an utterance's rows beyond it are not written).  d_out must
+ * not overlap d_in: a lane reads rows that other lanes write.  Any C >= 1, any row count including 0 and 1.  B == 0 or
+ * max_rows == 0 returns 0 without looking at the pointers; bad sizes, strides and null pointers return
+ * PDS_STAGES_ERR_INVALID before any HIP call, as does a batch whose B * ceil(max_rows / refresh) * C lanes need more
+ * than 2^31 - 1 blocks of 256 (split the batch).
+ * --------------------------------------------------------------------------------- */
+int32_t pds_sliding_cmvn_rows_f32(const float *d_in, int64_t in_stride, const int64_t *d_row_off,
+                                  const int64_t *d_nrows, int32_t B, int64_t max_rows, int32_t C, int32_t cmn_window,
+                                  int32_t min_window, int32_t center, int32_t norm_vars, int32_t refresh, float *d_out,
+                                  int64_t out_stride, void *stream);
+int32_t pds_sliding_cmvn_rows_f64(const double *d_in, int64_t in_stride, const int64_t *d_row_off,
+                                  const int64_t *d_nrows, int32_t B, int64_t max_rows, int32_t C, int32_t cmn_window,
+                                  int32_t min_window, int32_t center, int32_t norm_vars, int32_t refresh, double *d_out,
+                                  int64_t out_stride, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * The same normalisation per stream across the ticks of batched streaming (StreamBatch(sliding_cmvn=...)): the causal
+ * window with min_window = 1, ws = max(0, t - W), we = t + 1, which needs nothing of the future.  The call runs once
+ * per tick, in place on the tick's statics in d_statics (contiguous rows of `coeffs` values), where the running CMVN
+ * call of libpds_amd.so would run: before the deltas.  Per stream the device keeps
+ *   a ring of its last W + 1 input rows, d_ring = T[capacity][W + 1][coeffs]: frame t lies in slot t % (W + 1), so the
+ *     slot frame t overwrites holds exactly the frame that leaves the window at t, frame t - W - 1;
+ *   its sums, d_sums = double[capacity][2][coeffs] (s1, then s2).
+ * One pool each, no ping-pong: a (stream, coefficient) pair is read and written by one thread of a call, which takes
+ * the tick's rows in order.  d_meta holds n entries of 8 int64:
+ *   [0] stream s (0 <= s < capacity)   [1] flags: bit 0 fresh (the stream has seen no frame: ring and sums are not read)
+ *   [2] first row of the stream's new statics in d_statics (row index)   [3] their number k (may be 0)
+ *   [4] frames t0 the stream has seen before this call (0 if fresh): the new rows are frames t0 .. t0 + k - 1
+ *   [5..7] reserved, 0
+ * and every row is normalised by the definition above (at a refresh frame the sums are rebuilt from the ring, in
+ * frame order), bit for bit what the offline call gives over the stream's whole sequence of statics with center = 0
+ * and min_window = 1.  An entry with k > 0 writes its k rows to the ring and its sums back.  Streams of one call are
+ * distinct.  d_statics may be NULL when no entry has rows.  n == 0 returns 0 without looking at the pointers; bad
+ * sizes and null pointers return PDS_STAGES_ERR_INVALID before any HIP call.
+ * --------------------------------------------------------------------------------- */
+int32_t pds_multistream_sliding_f32(float *d_statics, float *d_ring, double *d_sums, int64_t capacity, int32_t coeffs,
+                                    int32_t cmn_window, int32_t norm_vars, int32_t refresh, const int64_t *d_meta,
+                                    int32_t n, void *stream);
+int32_t pds_multistream_sliding_f64(double *d_statics, double *d_ring, double *d_sums, int64_t capacity,
+                                    int32_t coeffs, int32_t cmn_window, int32_t norm_vars, int32_t refresh,
+                                    const int64_t *d_meta, int32_t n, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* PDS_AMD_STAGES_H */

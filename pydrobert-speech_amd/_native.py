@@ -1,4 +1,5 @@
-"""ctypes binding of ``libpds_amd.so`` (C ABI: ``include/pds_amd.h``).
+"""ctypes binding of ``libpds_amd.so`` (C ABI: ``include/pds_amd.h``) and of ``libpds_amd_stages.so``, the stage
+kernels outside the fused kernel's instantiation matrix (C ABI: ``include/pds_amd_stages.h``).
 
 There is deliberately no fallback: if the shared library is missing or a compute call
 is made without a HIP device, an exception is raised.  Nothing in this package computes
@@ -11,6 +12,8 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_int32, c_int64, c_v
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PDS_AMD_LIB selects another build of the same library (kernel tuning experiments)
 LIB_PATH = os.environ.get("PDS_AMD_LIB") or os.path.join(_HERE, "csrc", "libpds_amd.so")
+# ... and PDS_AMD_STAGES_LIB another build of the stages library
+STAGES_LIB_PATH = os.environ.get("PDS_AMD_STAGES_LIB") or os.path.join(_HERE, "csrc", "libpds_amd_stages.so")
 
 PDS_OK = 0
 
@@ -226,7 +229,26 @@ SIGNATURES = {
     "pds_allreduce_sum_f64": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
+_SLIDING_ROWS_ARGS = [
+    c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_int32,  # d_in, in_stride, d_row_off, d_nrows, B, max_rows, C
+    c_int32, c_int32, c_int32, c_int32, c_int32,  # cmn_window, min_window, center, norm_vars, refresh
+    c_void_p, c_int64, c_void_p,  # d_out, out_stride, stream
+]
+_MS_SLIDING_ARGS = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,
+                    c_void_p]
+
+# name -> (restype, argtypes); every symbol include/pds_amd_stages.h declares
+STAGES_SIGNATURES = {
+    "pds_stages_version": (c_int32, []),
+    "pds_stages_last_error": (c_char_p, []),
+    "pds_sliding_cmvn_rows_f32": (c_int32, _SLIDING_ROWS_ARGS),
+    "pds_sliding_cmvn_rows_f64": (c_int32, _SLIDING_ROWS_ARGS),
+    "pds_multistream_sliding_f32": (c_int32, _MS_SLIDING_ARGS),
+    "pds_multistream_sliding_f64": (c_int32, _MS_SLIDING_ARGS),
+}
+
 _lib = None
+_stages_lib = None
 
 
 def lib() -> ctypes.CDLL:
@@ -254,6 +276,28 @@ def lib() -> ctypes.CDLL:
     return _lib
 
 
+def stages_lib() -> ctypes.CDLL:
+    """The loaded stages library; raises :class:`NativeError` if it has not been built"""
+    global _stages_lib
+    if _stages_lib is None:
+        if not os.path.exists(STAGES_LIB_PATH):
+            raise NativeError(
+                f"{STAGES_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
+                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
+            )
+        try:  # (torch's HIP runtime first, as for lib())
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        loaded = ctypes.CDLL(STAGES_LIB_PATH)
+        for name, (restype, argtypes) in STAGES_SIGNATURES.items():
+            fn = getattr(loaded, name)  # AttributeError if the .so is stale
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _stages_lib = loaded
+    return _stages_lib
+
+
 def last_error() -> str:
     return lib().pds_last_error().decode("utf-8", "replace")
 
@@ -265,6 +309,15 @@ def check(rc: int, what: str) -> None:
             raise ValueError(f"{what}: {msg}")
         if rc == -3:
             raise MemoryError(f"{what}: {msg}")
+        raise NativeError(f"{what}: {msg} (code {rc})")
+
+
+def check_stages(rc: int, what: str) -> None:
+    """:func:`check` for a call into the stages library, which keeps its own error string"""
+    if rc != PDS_OK:
+        msg = stages_lib().pds_stages_last_error().decode("utf-8", "replace")
+        if rc == -1:
+            raise ValueError(f"{what}: {msg}")
         raise NativeError(f"{what}: {msg} (code {rc})")
 
 

@@ -17,7 +17,9 @@ Same command line and on-disk result as the reference's tool -- a text map of
   buffer and goes through ONE launch per stage: dither, pre-emphasis (fused into the frame
   loader when it is the last pre-processor), the fused STFT/filter-bank kernel, then each
   post-processor over the packed rows (a ``Cepstra`` -- ``--postprocess '[{"name": "mfcc", "num_ceps": 13}]'`` --
-  works row by row, so the whole batch is one call and one launch, and the row offsets stay as they are);
+  works row by row, so the whole batch is one call and one launch, and the row offsets stay as they are; a
+  ``SlidingCMVN`` -- ``{"name": "sliding_cmvn", "cmn_window": 600}`` -- normalises every utterance by itself in one
+  launch over the packed rows, ``SlidingCMVN.apply_rows``);
 * features come back in one transfer per batch and are written with ``torch.save``.
 
 Differences from the reference, by design: arithmetic is float32 unless ``--precision
@@ -38,7 +40,7 @@ import numpy as np
 
 from .alias import alias_factory_subclass_from_arg
 from .compute import FrameComputer
-from .post import Cepstra, Deltas, PostProcessor, Stack, Standardize
+from .post import Cepstra, Deltas, PostProcessor, SlidingCMVN, Stack, Standardize
 from .pre import Dither, Preemphasize, PreProcessor
 from .util import SIGNAL_SOURCES, read_signal
 
@@ -243,6 +245,9 @@ class FeatureDirWriter:
                     pass  # a pad mode the row kernel does not have: per utterance below
             elif isinstance(post, Cepstra):
                 feats = post.apply(feats, axis=-1)  # row by row: the whole packed batch in one launch, same rows
+                continue
+            elif isinstance(post, SlidingCMVN) and feats.dtype in (torch.float32, torch.float64):
+                feats = post.apply_rows(feats, rows)  # every utterance by itself, the packed batch in one launch
                 continue
             elif isinstance(post, Standardize) and post.have_stats:
                 feats = post.apply(feats, axis=-1)  # one global transform: the whole batch at once

@@ -16,6 +16,7 @@ samples of up to `capacity` streams in a device pool and takes every stream that
     sb = StreamBatch(computer, capacity=4096, stack=Stack(3))      # every 3 rows of a stream side by side, see below
     sb = StreamBatch(computer, capacity=4096, dither=Dither(1.0, seed=5))   # Dither over every stream's whole signal
     sb = StreamBatch(computer, capacity=4096, cepstra=Cepstra(13))  # cepstral coefficients of every row, see below
+    sb = StreamBatch(computer, capacity=4096, sliding_cmvn=SlidingCMVN(600, 1))  # sliding-window CMVN, see below
 
 Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
 the same chunks: the same row counts, dtype and -- for float32 and float64 samples -- the same values bit for bit as
@@ -35,7 +36,7 @@ Both kinds of tick, of this class and of :class:`multistream_si.SiStreamBatch`, 
 :func:`_TickBatch._tick`: the streams' spans (where each one's samples lie in what the feature launch reads), the
 upload -- laid out by :func:`_tick_layout` and addressed by section name through :class:`_Upload`, nowhere by hand --,
 the assemble launch (``compute_chunks`` only), the feature launch, the commit or reset of the host state, then the
-cepstra, the cmvn, the deltas and the stack launch.  A class adds what differs through four hooks: its host state, the order in
+cepstra, the cmvn (or the sliding-window cmvn), the deltas and the stack launch.  A class adds what differs through four hooks: its host state, the order in
 which the emitting streams launch, its extra rows of launch metadata, and the feature launch itself.  A new stage is
 one edit there.
 
@@ -100,6 +101,20 @@ returns the stream to P.  With `deltas` the deltas are taken of the normalised s
 add-deltas``), so the history pool holds normalised rows and a stream's rows are ``deltas.apply(Y, axis=0)``.
 :func:`StreamBatch.cmvn_stats` returns the streams' current tables.
 
+With `sliding_cmvn` (a :class:`post.SlidingCMVN` with ``center=False`` and ``min_window=1``) every static row is
+normalised by the mean (and variance) of the stream's last ``W + 1 = cmn_window + 1`` static rows, itself included --
+the stage runs where `cmvn` runs, after `cepstra` and before `deltas` and `stack`, and the two exclude each other.  A
+stream's rows are ``sliding_cmvn.apply(X)`` of the whole sequence X of its statics since its start or last
+``finalize``, bit for bit, whatever the cuts: the sums are rebuilt every `refresh` frames of the stream, as offline,
+so rounding does not drift however long the stream runs, and a NaN or infinite row stops affecting the stream at the
+first refresh after it has left the window.  A centred window needs ``W // 2`` frames of the future and
+``min_window > 1`` makes the first rows wait for later ones: both are refused.  :class:`SlidingState` counts the frames
+per stream on the host; the device keeps, per stream, a ring of its last ``W + 1`` static rows in `dtype` -- frame t in
+slot ``t % (W + 1)``, so the slot a frame overwrites holds exactly the frame that leaves the window -- and its two sums
+in float64, and one launch per tick (``pds_multistream_sliding_*`` of the stages library, ``csrc/sliding.hip``) takes
+every stream's new rows in order, in place.  ``finalize`` normalises the last rows like any others and returns the
+stream to fresh.
+
 With `stack` (a :class:`post.Stack`: frames along the row axis, ``pad_mode`` None, "edge" or "constant") every
 ``nv = num_vectors`` consecutive rows of a stream become one row of ``nv`` times the width -- the last stage, after
 `cmvn` and `deltas`: a stream's rows, concatenated over its ``compute_chunks`` calls and its ``finalize``, are
@@ -125,16 +140,18 @@ import numpy as np
 from . import _native, config
 from .alias import alias_factory_subclass_from_arg
 from .compute import PackedLayout, ShortTimeFourierTransformFrameComputer
-from .post import Cepstra, Deltas, PostProcessor, Stack, Standardize
+from .post import Cepstra, Deltas, PostProcessor, SlidingCMVN, Stack, Standardize
 from .pre import Dither, Preemphasize, PreProcessor, dither_keys
 
-__all__ = ["CmvnState", "DeltaState", "DitherState", "StackState", "StreamBatch", "StreamState", "streaming_cepstra",
-           "streaming_cmvn", "streaming_deltas", "streaming_dither", "streaming_preemphasis", "streaming_stack"]
+__all__ = ["CmvnState", "DeltaState", "DitherState", "SlidingState", "StackState", "StreamBatch", "StreamState",
+           "streaming_cepstra", "streaming_cmvn", "streaming_deltas", "streaming_dither", "streaming_preemphasis",
+           "streaming_sliding_cmvn", "streaming_stack"]
 
 _FIELDS = 8  # int64 per entry of pds_multistream_assemble's metadata (include/pds_amd.h)
 _DFIELDS = 8  # ... and of pds_multistream_deltas'
 _CFIELDS = 8  # ... and of pds_multistream_cmvn's
 _KFIELDS = 8  # ... and of pds_multistream_stack's
+_WFIELDS = 8  # ... and of pds_multistream_sliding's (include/pds_amd_stages.h)
 _PAD_NONE, _PAD_CONSTANT, _PAD_EDGE = 0, 1, 2  # the `pad` of pds_multistream_stack
 _FLAG_FRESH = 1  # of the flags word of the cmvn metadata: the stream starts from the prior statistics
 _FLAG_FINAL = 2  # (bit 0 of the flags word is the pool half)
@@ -577,6 +594,76 @@ class CmvnState:
         meta[:, 5:] = 0
 
 
+def streaming_sliding_cmvn(sliding_cmvn) -> Optional[SlidingCMVN]:
+    """`sliding_cmvn` as :class:`StreamBatch` takes it -- a :class:`post.SlidingCMVN` or what
+    ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one (``{"name": "sliding_cmvn", "cmn_window": 600,
+    "min_window": 1}``) -> the ``SlidingCMVN``, or None for ``sliding_cmvn=None``; ``ValueError`` for anything else, for
+    a centred window and for ``min_window != 1``, which a stream cannot serve"""
+    if sliding_cmvn is None:
+        return None
+    try:
+        sliding_cmvn = alias_factory_subclass_from_arg(PostProcessor, sliding_cmvn)
+    except (KeyError, TypeError) as e:
+        raise ValueError(f"StreamBatch: sliding_cmvn is no post-processor ({e!r})") from None
+    if not isinstance(sliding_cmvn, SlidingCMVN):
+        raise ValueError("StreamBatch: sliding_cmvn must be a post.SlidingCMVN")
+    if sliding_cmvn.center:
+        raise ValueError("StreamBatch: sliding_cmvn must use center=False: a centred window needs cmn_window // 2 "
+                         "frames of the future, which a stream does not have")
+    if sliding_cmvn.min_window != 1:
+        raise ValueError("StreamBatch: sliding_cmvn must use min_window=1: with a larger one a stream's first rows "
+                         "would have to wait for later ones (holding rows back is not served)")
+    return sliding_cmvn
+
+
+class SlidingState:
+    """Host bookkeeping of the sliding-window CMVN of many streams.  Needs no device.
+
+    `window`: ``cmn_window``; the device ring holds ``window + 1`` rows per stream.  Per stream: ``seen`` static frames
+    normalised since its start or last ``finalize`` -- its next row is frame ``seen`` of its utterance, which goes to
+    slot ``seen % (window + 1)`` of its ring; a stream that has none is ``fresh``: its ring and sums are not read.
+    """
+
+    def __init__(self, capacity: int, window: int, refresh: Optional[int] = None):
+        capacity, window = int(capacity), int(window)
+        refresh = window if refresh is None else int(refresh)
+        if capacity <= 0 or window <= 0 or refresh <= 0:
+            raise ValueError("capacity, window and refresh must be positive")
+        self.capacity, self.window, self.refresh = capacity, window, refresh
+        self.ring_rows = window + 1
+        self.seen = np.zeros(capacity, dtype=np.int64)
+
+    @property
+    def fresh(self) -> np.ndarray:
+        return self.seen == 0
+
+    def step(self, ids: np.ndarray, k: np.ndarray, final: bool = False) -> dict:
+        """What a tick that brings streams `ids` `k` new static frames does, without changing the state: per stream
+        the frames `seen` before the tick, whether it is `fresh`, and the frames seen after it"""
+        k = np.asarray(k, dtype=np.int64)
+        seen = self.seen[ids]
+        return dict(k=k, seen=seen, fresh=seen == 0, next_seen=seen + k, final=bool(final))
+
+    def commit(self, ids: np.ndarray, step: dict) -> None:
+        if step["final"]:
+            self.reset(ids)  # (the next utterance on the id starts with an empty window)
+        else:
+            self.seen[ids] = step["next_seen"]
+
+    def reset(self, ids: np.ndarray) -> None:
+        self.seen[ids] = 0
+
+    def fill_meta(self, meta: np.ndarray, ids: np.ndarray, step: dict, static_rows: np.ndarray) -> None:
+        """pds_multistream_sliding's metadata of a tick into `meta` (int64[n, 8]); `static_rows`: each stream's first
+        row in the tick's statics"""
+        meta[:, 0] = ids
+        meta[:, 1] = step["fresh"] * _FLAG_FRESH
+        meta[:, 2] = static_rows
+        meta[:, 3] = step["k"]
+        meta[:, 4] = step["seen"]
+        meta[:, 5:] = 0
+
+
 def streaming_stack(stack) -> Optional[Tuple[Stack, int, int, float]]:
     """`stack` as :class:`StreamBatch` takes it -- a :class:`post.Stack` or what
     ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one -> ``(Stack, num_vectors, pad, fill)`` with `pad`
@@ -738,13 +825,15 @@ def _place(sections):
 
 
 @functools.lru_cache(maxsize=256)  # (a batch's ticks repeat a few sizes: each is placed once)
-def _tick_layout(n, E, launch_rows, chunks, deltas, cmvn, stack=False, dither=False):
+def _tick_layout(n, E, launch_rows, chunks, deltas, cmvn, stack=False, dither=False, sliding=False):
     """The sections behind the samples in the upload of a tick over `n` streams of which `E` emit frames, placed: the
     assemble metadata and the tile prefix (`chunks`: a ``compute_chunks`` tick; ``finalize`` has neither, and no
     samples), the launch metadata -- `launch_rows` rows, one column per emitting stream --, the deltas metadata and
     the element prefix (`deltas`), the cmvn metadata (`cmvn`), the stack metadata and its element prefix (`stack`), the
-    positions and keys of the dither (`dither`, in a ``compute_chunks`` tick)"""
-    # (a batch without `stack` / `dither` has the layout it had before there was one: their sections are not placed at all)
+    positions and keys of the dither (`dither`, in a ``compute_chunks`` tick), the sliding-window cmvn metadata
+    (`sliding`)"""
+    # (a batch without `stack` / `dither` / `sliding` has the layout it had before there was one: their sections are
+    # not placed at all)
     return _place((("assemble", (n if chunks else 0, _FIELDS)),
                    ("tiles", (n + 1 if chunks else 0,)),
                    ("launch", (launch_rows, E)),
@@ -752,7 +841,8 @@ def _tick_layout(n, E, launch_rows, chunks, deltas, cmvn, stack=False, dither=Fa
                    ("elems", (n + 1 if deltas else 0,)),
                    ("cmvn", (n if cmvn else 0, _CFIELDS)))
                   + ((("stack", (n, _KFIELDS)), ("stack_elems", (n + 1,))) if stack else ())
-                  + ((("dither", (n if chunks else 0, 2)),) if dither else ()))
+                  + ((("dither", (n if chunks else 0, 2)),) if dither else ())
+                  + ((("sliding", (n, _WFIELDS)),) if sliding else ()))
 
 
 class _TickBatch:
@@ -768,7 +858,7 @@ class _TickBatch:
     _launch_extra = ()
 
     def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None, cmvn=None,
-                 cmvn_running=True, stack=None, dither=None, cepstra=None):
+                 cmvn_running=True, stack=None, dither=None, cepstra=None, sliding_cmvn=None):
         # every argument is read before a device is touched
         if not isinstance(computer, self._computer_type):
             raise TypeError(self._wrong_computer)
@@ -784,6 +874,9 @@ class _TickBatch:
             pspec._split(width)
             width = pspec.num_ceps
         cspec = streaming_cmvn(cmvn, bool(cmvn_running), width)
+        wspec = streaming_sliding_cmvn(sliding_cmvn)
+        if cspec is not None and wspec is not None:
+            raise ValueError("StreamBatch: cmvn and sliding_cmvn both normalise the statics: give one of them")
         kspec = streaming_stack(stack)
         nspec = streaming_dither(dither)
         self.state, row_length = self._new_state(computer, capacity)
@@ -847,6 +940,17 @@ class _TickBatch:
                 self._sums = torch.empty((self.capacity, 2, self._F), dtype=torch.float64, device=self.device)
             self._cmvn_fn = (self._lib.pds_multistream_cmvn_f32 if dtype == np.float32
                              else self._lib.pds_multistream_cmvn_f64)
+        self.wstate = self._ring = self._wsums = None
+        if wspec is not None:
+            self._sliding = wspec
+            self.wstate = SlidingState(self.capacity, wspec.cmn_window, wspec.refresh)
+            stages = _native.stages_lib()
+            # every stream's last cmn_window + 1 static rows and its two sums (a fresh stream's are not read: no fill)
+            self._ring = torch.empty((self.capacity, self.wstate.ring_rows, self._F), dtype=self._tdtype,
+                                     device=self.device)
+            self._wsums = torch.empty((self.capacity, 2, self._F), dtype=torch.float64, device=self.device)
+            self._sliding_fn = (stages.pds_multistream_sliding_f32 if dtype == np.float32
+                                else stages.pds_multistream_sliding_f64)
         self.num_coeffs = self._C
         self.kstate = self._pending = None
         if kspec is not None:
@@ -962,6 +1066,7 @@ class _TickBatch:
     def close(self) -> None:
         """Release the pools and the pinned buffers; the object cannot be used afterwards"""
         self._pool = self._hist = self._prev = self._sums = self._d_prior = self._pending = None
+        self._ring = self._wsums = None
         self._up = [None, None]
         self._up_events = [None, None]
         self._down = None
@@ -1054,7 +1159,8 @@ class _TickBatch:
         order = self._emit_order(step, np.flatnonzero(k > 0))
         up = _Upload(ns, _tick_layout(n, len(order), 4 + len(self._launch_extra), not final, self.dstate is not None,
                                       self.cstate is not None, self.kstate is not None,
-                                      *((True,) if self.nstate is not None else ())))
+                                      *((self.nstate is not None, True) if self.wstate is not None
+                                        else (True,) if self.nstate is not None else ())))
         slot, buf = self._staging(up.words)
         up.pinned = buf.numpy()
         if ns:
@@ -1086,6 +1192,9 @@ class _TickBatch:
         if self.cstate is not None:
             cstep = self.cstate.step(ids, k, final=final)
             self.cstate.fill_meta(up.host("cmvn"), ids, cstep, row0)
+        if self.wstate is not None:
+            wstep = self.wstate.step(ids, k, final=final)
+            self.wstate.fill_meta(up.host("sliding"), ids, wstep, row0)
         if self.kstate is not None:  # over what the stages before it return: the statics, or the rows of the deltas
             new = dstep["out_rows"] if self.dstate is not None else rows
             kstep = self.kstate.step(ids, np.diff(new), final=final)
@@ -1115,6 +1224,8 @@ class _TickBatch:
             feats = self._cepstra.apply(feats)  # one launch on `stream`, none without rows
         if self.cstate is not None:
             self._cmvn_launch(feats, up.dev("cmvn"), ids, cstep, stream)
+        if self.wstate is not None:
+            self._sliding_launch(feats, up.dev("sliding"), ids, wstep, stream)
         if self.dstate is not None:
             feats, rows = self._delta_launch(feats, up.dev("deltas"), up.dev("elems"), ids, dstep, elems, stream)
         if self.kstate is not None:
@@ -1155,6 +1266,16 @@ class _TickBatch:
                                stream.cuda_stream)
             _native.check(rc, "pds_multistream_cmvn")
         self.cstate.commit(ids, cstep)
+
+    def _sliding_launch(self, statics, d_meta, ids, wstep, stream):
+        """one pds_multistream_sliding launch, in place over the tick's `statics` (none in a tick without new rows: no
+        stream's ring or sums change then)"""
+        if statics.shape[0]:
+            rc = self._sliding_fn(statics.data_ptr(), self._ring.data_ptr(), self._wsums.data_ptr(), self.capacity,
+                                  self._F, self._sliding.cmn_window, int(self._sliding.norm_vars),
+                                  self._sliding.refresh, d_meta.data_ptr(), len(ids), stream.cuda_stream)
+            _native.check_stages(rc, "pds_multistream_sliding")
+        self.wstate.commit(ids, wstep)
 
     def _delta_launch(self, statics, d_meta, d_elem_prefix, ids, dstep, elems, stream):
         """one pds_multistream_deltas launch over the tick's `statics`: the rows due and the next histories"""
@@ -1254,6 +1375,17 @@ class StreamBatch(_TickBatch):
     ``num_coeffs``), so a stream's rows are ``stack(deltas(cmvn(cepstra(statics))))`` of the offline objects over its
     whole utterance, bit for bit.  ``ValueError`` here if the computer's width does not admit `num_ceps`.  No state,
     no additional device memory, no change of a tick's upload; one more launch per tick that has rows.
+
+    `sliding_cmvn`: a :class:`post.SlidingCMVN` (or what ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes
+    one: ``{"name": "sliding_cmvn", "cmn_window": 600, "min_window": 1}``) with ``center=False`` and ``min_window=1``;
+    ``None``: none.  It stands where `cmvn` stands (after `cepstra`, before `deltas` and `stack`; giving both is
+    refused): every static row is normalised over the stream's last ``cmn_window + 1`` static rows, and a stream's rows
+    are ``sliding_cmvn.apply(X)`` of its whole sequence of statics X, bit for bit (the module docstring has the
+    arithmetic and why a centred window and ``min_window > 1`` are refused).  ``finalize`` returns a stream to fresh.
+    Additional device memory: per stream a ring of ``cmn_window + 1`` rows of F elements of `dtype` and ``2 * F``
+    float64 sums -- 96 KB per stream at ``cmn_window = 600``, ``F = 40`` and float32 (601 * 40 * 4 + 640 bytes), 394 MB
+    at the default capacity of 4096: size `capacity` to the streams that are live.  A tick's upload grows by eight
+    words per stream.
 
     `dither`: a :class:`pre.Dither` (or what ``alias_factory_subclass_from_arg(PreProcessor, ...)`` makes one:
     ``"dither"``, ``{"name": "dither", "coeff": 1.0, "seed": 5}``); ``None`` or a coefficient of 0: none.  Every

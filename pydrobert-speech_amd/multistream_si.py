@@ -183,8 +183,9 @@ class SiStreamBatch(_TickBatch):
     """``compute_chunk`` / ``finalize`` of many streams of one short-integration computer, one tick per call
 
     `computer`: a :class:`si.ShortIntegrationFrameComputer` (its plan and configuration are used; its own streaming
-    state is not touched).  `capacity`, `dtype`, `deltas`, `preemphasis`, `cmvn`, `cmvn_running`, `stack`, `dither`, `cepstra`
-    and every method (``cmvn_stats`` and ``dither_seeds`` among them): as :class:`multistream.StreamBatch` -- with `dither`
+    state is not touched).  `capacity`, `dtype`, `deltas`, `preemphasis`, `cmvn`, `cmvn_running`, `stack`, `dither`, `cepstra`,
+    `sliding_cmvn` (sliding-window CMVN in the place of `cmvn`; its ring of ``cmn_window + 1`` rows per stream is added
+    to the device memory below) and every method (``cmvn_stats`` and ``dither_seeds`` among them): as :class:`multistream.StreamBatch` -- with `dither`
     every stream's raw signal is dithered across ticks, before the pre-emphasis; with `cmvn` the static rows are
     standardised frame by frame, running or by fixed statistics, before the deltas are taken, and with `stack` the rows
     are stacked last.  Device memory: the carry pool, ``2 * capacity * row_length`` samples with

@@ -1,4 +1,4 @@
-"""Post-processors on the hot path: ``Deltas``, ``Standardize`` / ``CMVN`` and ``Cepstra``.
+"""Post-processors on the hot path: ``Deltas``, ``Standardize`` / ``CMVN``, ``Cepstra`` and ``SlidingCMVN``.
 
 Same classes, aliases, arguments and error behaviour as the reference's (post.py:38-491);
 the element-wise and stencil arithmetic runs in HIP kernels (``csrc/post.hip``) -- there
@@ -7,6 +7,9 @@ and finalises the ``O(num_coeffs)`` mean/scale vectors of CMVN.
 
 ``Cepstra`` is not in the reference: the DCT-II and lifter that turn log filter-bank outputs into cepstral
 coefficients (MFCCs), one HIP kernel over the rows with the matrix built on the host in float64.
+
+``SlidingCMVN`` is not in the reference either: mean (and variance) normalisation over a sliding window of frames,
+Kaldi's ``apply-cmvn-sliding``, one HIP kernel of the stages library (``csrc/sliding.hip``) over a packed ragged batch.
 
 ``Stack`` moves data only: views for a single tensor, one copy
 kernel for a packed ragged batch.  CMVN statistics files (``rfilename``, ``save``) go through
@@ -21,7 +24,7 @@ import numpy as np
 from . import _native
 from .alias import AliasedFactory
 
-__all__ = ["CMVN", "Cepstra", "Deltas", "PostProcessor", "Stack", "Standardize"]
+__all__ = ["CMVN", "Cepstra", "Deltas", "PostProcessor", "SlidingCMVN", "Stack", "Standardize"]
 
 
 class PostProcessor(AliasedFactory):
@@ -789,3 +792,146 @@ class Cepstra(PostProcessor):
             out.copy_(rows[:, :copy])
         out = out.reshape(lead + (copy + K,)).movedim(-1, axis)
         return out if on_gpu else out.cpu().numpy()
+
+
+# ------------------------------------------------------------------ SlidingCMVN ------
+
+
+def _positive_int(value, what):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 1:
+        raise ValueError(f"SlidingCMVN: {what} must be a positive integer, got {value!r}")
+    if value >= 1 << 31:
+        raise ValueError(f"SlidingCMVN: {what} must be below 2**31, got {value!r}")
+    return int(value)
+
+
+def _flag(value, what):
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"SlidingCMVN: {what} must be a bool, got {value!r}")
+    return bool(value)
+
+
+class SlidingCMVN(PostProcessor):
+    """Mean (and variance) normalisation over a sliding window of frames: Kaldi's ``apply-cmvn-sliding``
+
+    `axis` of :func:`apply` is the *coefficient* axis; time is the axis in front of it (rows of a ``(frames, coeffs)``
+    matrix).  For an utterance of T frames, frame t and ``W = cmn_window`` the window ``[ws, we)`` is
+
+        center:      ws = t - W // 2;  we = ws + W
+        not center:  ws = t - W;       we = t + 1
+        if ws < 0:                 we -= ws;  ws = 0
+        if not center and we > t:  we = max(t + 1, min_window)
+        if we > T:                 ws -= we - T;  we = T;  ws = max(ws, 0)
+
+    -- Kaldi's rule, its causal window of ``W + 1`` frames included.  ``0 <= ws <= t < we <= T``, ``ws`` and ``we``
+    each move by 0 or 1 from one frame to the next, and the window holds at most ``max(W + 1, min_window)`` frames.
+
+    The arithmetic is fixed: per coefficient, in float64, x widened first, every operation rounded separately,
+    division and square root correctly rounded.
+
+        t % refresh == 0:  s1 = s2 = 0, then for u = ws .. we - 1 in order  s1 += x_u;  s2 += x_u * x_u
+        other frames:      if ws moved  s1 -= x_old;  s2 -= x_old * x_old  (the frame that left), and then, if we moved,
+                           s1 += x_new;  s2 += x_new * x_new  (the frame that entered)
+        n = we - ws;  mean = s1 / n;  y = x_t - mean
+        norm_vars:  y = 0 if n == 1, else  var = s2 / n - mean * mean;  var = 1e-10 unless var > 1e-10;
+                    y = y * (1 / sqrt(var))
+
+    and y is rounded once to the input's type: float32 gives float32, float64 gives float64, anything else is widened
+    to float64 first.  `refresh` (default: `cmn_window`) is part of the result, in its last bits: the sums are rebuilt
+    every `refresh` frames, so segments of `refresh` frames are computed in parallel, rounding does not drift over a
+    long stream, and a NaN or infinite frame stops affecting the output at the first refresh after it has left the
+    window.  The same object gives the same bits offline and, with ``center=False`` and ``min_window=1``, streamed
+    (``StreamBatch(sliding_cmvn=...)``).
+    """
+
+    aliases = {"sliding_cmvn", "cmvn_sliding", "sliding"}
+
+    def __init__(self, cmn_window: int = 600, min_window: int = 100, center: bool = False, norm_vars: bool = False,
+                 refresh: Optional[int] = None):
+        self.cmn_window = _positive_int(cmn_window, "cmn_window")
+        self.min_window = _positive_int(min_window, "min_window")
+        self.center = _flag(center, "center")
+        self.norm_vars = _flag(norm_vars, "norm_vars")
+        self.refresh = self.cmn_window if refresh is None else _positive_int(refresh, "refresh")
+
+    def apply_rows(self, feats, row_offsets, out=None):
+        """Every utterance of a packed ragged batch normalised by itself, in one launch on the GPU
+
+        `feats`: ``(total_rows, C)`` float32 or float64 GPU tensor (rows may be strided: a column slice of a wider
+        tensor), utterance b in rows ``row_offsets[b]:row_offsets[b+1]``; empty and one-row utterances are allowed.
+        Returns a tensor of the same shape and dtype (`out`, if given: it must not share memory with `feats`).
+        """
+        torch = _native.require_device()
+        lib = _native.stages_lib()
+        if not _is_gpu_tensor(feats) or feats.dtype not in (torch.float32, torch.float64) or feats.dim() != 2:
+            raise ValueError("feats must be a 2-D float32 or float64 GPU tensor")
+        if feats.shape[1] and feats.stride(1) != 1:
+            feats = feats.contiguous()
+        R, C = feats.shape
+        rows = np.ascontiguousarray(row_offsets, dtype=np.int64)
+        if rows.ndim != 1 or len(rows) < 1 or (np.diff(rows) < 0).any() or (len(rows) and (rows[0] < 0 or rows[-1] > R)):
+            raise ValueError("row_offsets must be B + 1 ascending row indices within feats")
+        if out is None:
+            out = torch.empty((R, C), dtype=feats.dtype, device=feats.device)
+        elif (not _is_gpu_tensor(out) or out.dtype != feats.dtype or out.device != feats.device
+              or tuple(out.shape) != (R, C) or (C and out.stride(1) != 1)):
+            raise ValueError("out must be a GPU tensor of feats' shape, dtype and device with contiguous rows")
+        elif R and C and out.untyped_storage().data_ptr() == feats.untyped_storage().data_ptr():
+            raise ValueError("out must not share memory with feats: the kernel works out of place")
+        B = len(rows) - 1
+        if B <= 0 or R == 0 or C == 0:
+            return out
+        meta, nrows = _rows_meta(rows, feats.device)
+        in_stride = feats.stride(0) if R > 1 else C
+        out_stride = out.stride(0) if R > 1 else C
+        if in_stride < C or out_stride < C:
+            raise ValueError("rows of feats and out must not overlap")
+        fn = lib.pds_sliding_cmvn_rows_f32 if feats.dtype == torch.float32 else lib.pds_sliding_cmvn_rows_f64
+        # one launch, unless the batch needs more lanes (utterances x segments x C) than a grid has blocks for
+        step = B
+        segs = -(-int(nrows.max()) // self.refresh)
+        if segs:
+            step = max(1, min(B, ((1 << 31) - 1) * 256 // (segs * C)))
+        with torch.cuda.device(feats.device):
+            for lo in range(0, B, step):
+                hi = min(B, lo + step)
+                rc = fn(feats.data_ptr(), in_stride, meta[0, lo:].data_ptr(), meta[1, lo:].data_ptr(), hi - lo,
+                        int(nrows[lo:hi].max()), C, self.cmn_window, self.min_window, int(self.center),
+                        int(self.norm_vars), self.refresh, out.data_ptr(), out_stride, _stream(torch, feats))
+                _native.check_stages(rc, "pds_sliding_cmvn_rows")
+        return out
+
+    def apply(self, features, axis: int = -1, in_place: bool = False):
+        on_gpu = _is_gpu_tensor(features)
+        if not on_gpu:
+            features = np.asarray(features)
+        shape = tuple(features.shape)
+        if len(shape) not in (2, 3):
+            raise ValueError("SlidingCMVN: expected (frames, coeffs) or (batch, frames, coeffs)")
+        axis = axis % len(shape)
+        torch = _native.require_device()
+        if on_gpu:
+            t = features if features.dtype in (torch.float32, torch.float64) else features.to(torch.float64)
+        else:
+            t = _to_device(features if features.dtype in (np.float32, np.float64) else features.astype(np.float64))
+        # coefficients last, time in front of them, utterances in front of that
+        moved = t.movedim(axis, -1)
+        lead = tuple(moved.shape)
+        T, C = lead[-2], lead[-1]
+        B = lead[0] if len(lead) == 3 else 1
+        if moved.dim() == 2 and moved.stride(1) == 1 and (moved.stride(0) >= C or T <= 1):
+            rows = moved  # a matrix whose rows are contiguous goes as it is, whatever its row stride
+        else:
+            rows = moved.reshape(B * T, C).contiguous()
+        out = self.apply_rows(rows, np.arange(B + 1, dtype=np.int64) * T)
+        out = out.reshape(lead).movedim(-1, axis)
+        if on_gpu:
+            if in_place and features.dtype == out.dtype:
+                features.copy_(out)
+                return features
+            return out
+        res = out.cpu().numpy()
+        if in_place and features.dtype == res.dtype and features.flags.writeable:
+            features[...] = res
+            return features
+        return res
