@@ -36,9 +36,19 @@ Both kinds of tick, of this class and of :class:`multistream_si.SiStreamBatch`, 
 :func:`_TickBatch._tick`: the streams' spans (where each one's samples lie in what the feature launch reads), the
 upload -- laid out by :func:`_tick_layout` and addressed by section name through :class:`_Upload`, nowhere by hand --,
 the assemble launch (``compute_chunks`` only), the feature launch, the commit or reset of the host state, then the
-cepstra, the cmvn (or the sliding-window cmvn), the deltas and the stack launch.  A class adds what differs through four hooks: its host state, the order in
-which the emitting streams launch, its extra rows of launch metadata, and the feature launch itself.  A new stage is
-one edit there.
+post stages.  A class adds what differs through four hooks: its host state, the order in which the emitting streams
+launch, its extra rows of launch metadata, and the feature launch itself.
+
+The post stages -- cepstra, cmvn or sliding-window cmvn, deltas, stack, in that order -- are objects of one protocol,
+:class:`_Stage`, which the constructor lists and the tick loops over twice.  A stage owns its parsed spec, its host
+state (``DeltaState`` ...; none for cepstra), its device pools, its typed entry point -- looked up when the stage is
+built, so a library without it is an ``AttributeError`` for the batch that asks for the stage and no other -- and the
+names of its upload sections; it tells its output width from its input width.  ``plan`` is the host half, before the
+upload: given every stream's first row in what enters the stage, it steps its state without changing it, fills its
+sections and returns every stream's first row in what leaves it.  ``launch`` is the device half, after the feature
+launch: its one launch and check, then the commit of its state.  ``release`` drops its pools.  A new stage is such a
+class, its place in the constructor's list and -- if it has metadata -- its sections in :func:`_tick_layout`; the
+dither and the pre-emphasis act inside the assemble launch and are no stages.
 
 With `deltas` (a :class:`post.Deltas`: "edge" padding, concatenated along the coefficient axis) a stream's rows are
 those of ``deltas.apply(X, axis=0)`` over the whole sequence X of its statics, bit for bit, delayed by the look-ahead
@@ -164,6 +174,24 @@ def _exclusive_cumsum(x: np.ndarray) -> np.ndarray:
     out = np.zeros(len(x) + 1, dtype=np.int64)
     np.cumsum(x, out=out[1:])
     return out
+
+
+def _post_processor(name: str, arg, kind):
+    """the shared opening of the ``streaming_*`` readers of the post stages: `arg`, keyword `name` of
+    :class:`StreamBatch`, as ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes it, which must be a `kind`"""
+    try:
+        arg = alias_factory_subclass_from_arg(PostProcessor, arg)
+    except (KeyError, TypeError) as e:
+        raise ValueError(f"StreamBatch: {name} is no post-processor ({e!r})") from None
+    if not isinstance(arg, kind):
+        raise ValueError(f"StreamBatch: {name} must be a post.{kind.__name__}")
+    return arg
+
+
+def _typed(lib, name: str, dtype):
+    """the entry point ``<name>_f32`` or ``<name>_f64`` of `lib` for samples of `dtype`; ``AttributeError`` from a
+    library that does not have it"""
+    return getattr(lib, name + ("_f32" if dtype == np.float32 else "_f64"))
 
 
 class _StreamWords:
@@ -396,12 +424,7 @@ def streaming_deltas(deltas) -> Optional[Tuple[Deltas, int, int]]:
     (``deltas=None`` or ``num_deltas == 0``); ``ValueError`` for settings batched streaming does not serve"""
     if deltas is None:
         return None
-    try:
-        deltas = alias_factory_subclass_from_arg(PostProcessor, deltas)
-    except (KeyError, TypeError) as e:
-        raise ValueError(f"StreamBatch: deltas is no post-processor ({e!r})") from None
-    if not isinstance(deltas, Deltas):
-        raise ValueError("StreamBatch: deltas must be a post.Deltas")
+    deltas = _post_processor("deltas", deltas, Deltas)
     K = int(deltas.num_deltas)
     if K < 0:
         raise ValueError("StreamBatch: num_deltas must not be negative")
@@ -498,12 +521,7 @@ def streaming_cepstra(cepstra) -> Optional[Cepstra]:
     -> the ``Cepstra``, or None for ``cepstra=None``; ``ValueError`` for anything else"""
     if cepstra is None:
         return None
-    try:
-        cepstra = alias_factory_subclass_from_arg(PostProcessor, cepstra)
-    except (KeyError, TypeError) as e:
-        raise ValueError(f"StreamBatch: cepstra is no post-processor ({e!r})") from None
-    if not isinstance(cepstra, Cepstra):
-        raise ValueError("StreamBatch: cepstra must be a post.Cepstra")
+    cepstra = _post_processor("cepstra", cepstra, Cepstra)
     return cepstra
 
 
@@ -516,12 +534,7 @@ def streaming_cmvn(cmvn, running: bool, num_coeffs: int) -> Optional[Tuple[Stand
     which a stream does not have"""
     if cmvn is None:
         return None
-    try:
-        cmvn = alias_factory_subclass_from_arg(PostProcessor, cmvn)
-    except (KeyError, TypeError) as e:
-        raise ValueError(f"StreamBatch: cmvn is no post-processor ({e!r})") from None
-    if not isinstance(cmvn, Standardize):
-        raise ValueError("StreamBatch: cmvn must be a post.Standardize")
+    cmvn = _post_processor("cmvn", cmvn, Standardize)
     prior = None
     if cmvn._stats is not None:
         prior = np.array(cmvn._stats, dtype=np.float64)
@@ -601,12 +614,7 @@ def streaming_sliding_cmvn(sliding_cmvn) -> Optional[SlidingCMVN]:
     a centred window and for ``min_window != 1``, which a stream cannot serve"""
     if sliding_cmvn is None:
         return None
-    try:
-        sliding_cmvn = alias_factory_subclass_from_arg(PostProcessor, sliding_cmvn)
-    except (KeyError, TypeError) as e:
-        raise ValueError(f"StreamBatch: sliding_cmvn is no post-processor ({e!r})") from None
-    if not isinstance(sliding_cmvn, SlidingCMVN):
-        raise ValueError("StreamBatch: sliding_cmvn must be a post.SlidingCMVN")
+    sliding_cmvn = _post_processor("sliding_cmvn", sliding_cmvn, SlidingCMVN)
     if sliding_cmvn.center:
         raise ValueError("StreamBatch: sliding_cmvn must use center=False: a centred window needs cmn_window // 2 "
                          "frames of the future, which a stream does not have")
@@ -672,12 +680,7 @@ def streaming_stack(stack) -> Optional[Tuple[Stack, int, int, float]]:
     serve"""
     if stack is None:
         return None
-    try:
-        stack = alias_factory_subclass_from_arg(PostProcessor, stack)
-    except (KeyError, TypeError) as e:
-        raise ValueError(f"StreamBatch: stack is no post-processor ({e!r})") from None
-    if not isinstance(stack, Stack):
-        raise ValueError("StreamBatch: stack must be a post.Stack")
+    stack = _post_processor("stack", stack, Stack)
     nv = stack.num_vectors
     if isinstance(nv, (bool, np.bool_)) or not isinstance(nv, (int, np.integer)) or nv < 1:
         raise ValueError("StreamBatch: num_vectors must be a positive integer")
@@ -845,6 +848,180 @@ def _tick_layout(n, E, launch_rows, chunks, deltas, cmvn, stack=False, dither=Fa
                   + ((("sliding", (n, _WFIELDS)),) if sliding else ()))
 
 
+class _Stage:
+    """One post stage of a batch `b`, as :func:`_TickBatch._tick` drives it (the protocol is in the module docstring).
+
+    `spec`: the parsed keyword.  `state`: the host state.  `width_in` / `width`: a row's coefficients entering and
+    leaving the stage.  `pools`: the device memory it keeps across ticks, by name.  `sections`: its sections of the
+    upload, the metadata first; :func:`_tick_layout` places them under the flag of the stage.  `counts`: for a stage
+    that makes rows of its own out of "what the stream keeps on the device, then the tick's new rows", the key of the
+    step's rows per stream; its second section is then the elements per entry as a prefix sum, and it launches in
+    every tick (a ``finalize`` returns rows without bringing any).  A stage without `counts` works on the rows where
+    they lie, and its launch is left out in a tick without rows: none of its pools changes then.  A subclass builds
+    the state and the pools, looks its typed entry point up -- there and nowhere else -- and has :func:`_run`, the
+    launch and its check, given the rows, the output (the rows themselves without `counts`), the device pointers of
+    the sections, the number of streams, the step and the stream's handle."""
+
+    sections = ()
+    state = counts = None
+
+    def __init__(self, batch, spec, width):
+        self.b, self.spec, self.width_in, self.width, self.pools = batch, spec, width, width, {}
+
+    def plan(self, up, ids, rows, final):
+        """the host half of a tick, before the upload: changes no state, fills the stage's sections of `up` and keeps
+        the step; `rows`: every stream's first row in what enters the stage (an exclusive prefix).  Returns the same of
+        what leaves it"""
+        step = self._step = self.state.step(ids, rows[1:] - rows[:-1], final=final)
+        out, extra = rows, ()
+        if self.counts:
+            out = step["out"] = _exclusive_cumsum(step[self.counts])
+            extra = (out[:-1], self.width_in)
+        step["elems"] = self.state.fill_meta(*map(up.host, self.sections), ids, step, rows[:-1], *extra)
+        return out
+
+    def launch(self, up, rows, ids, stream):
+        """the device half, after the feature launch: the stage's one launch over the `rows` that enter it, then the
+        commit of its host state.  Returns the rows that leave it"""
+        step, b, out = self._step, self.b, rows
+        if self.counts:
+            out = b._torch.empty((int(step["out"][-1]), self.width), dtype=b._tdtype, device=b.device)
+        if self.counts or rows.shape[0]:
+            self._run(rows, out, [up.dev(name).data_ptr() for name in self.sections], len(ids), step,
+                      stream.cuda_stream)
+        self.state.commit(ids, step)
+        return out
+
+    def release(self):
+        self.pools = {}
+
+
+class _CepstraStage(_Stage):
+    """`cepstra`: a row depends on nothing but itself -- no state, no pool, no section"""
+
+    def __init__(self, batch, spec, width):
+        super().__init__(batch, spec, width)
+        self.width = spec.num_ceps
+
+    def plan(self, up, ids, rows, final):
+        return rows
+
+    def launch(self, up, rows, ids, stream):
+        return self.spec.apply(rows)  # one launch on `stream`, none without rows
+
+
+class _CmvnStage(_Stage):
+    """`cmvn`: `spec` is :func:`streaming_cmvn`'s ``(Standardize, prior, norm_var)`` and whether the statistics run.
+    Pools: ``sums``, float64 ``(capacity, 2, F)`` (running statistics only; a fresh stream's slot is never read: no
+    fill), and ``prior``, the statistics passed in without their count (if any)"""
+
+    sections = ("cmvn",)
+
+    def __init__(self, batch, spec, width):
+        super().__init__(batch, spec, width)
+        _, self.prior, self._norm_var, running = spec
+        torch = batch._torch
+        self.state = CmvnState(batch.capacity, int(self.prior[0, -1]) if self.prior is not None else 0, running)
+        if self.prior is not None:
+            self.pools["prior"] = torch.from_numpy(np.ascontiguousarray(self.prior[:, :-1])).to(batch.device)
+        if running:
+            self.pools["sums"] = torch.empty((batch.capacity, 2, width), dtype=torch.float64, device=batch.device)
+        self._fn = _typed(batch._lib, "pds_multistream_cmvn", batch.dtype)
+
+    def _run(self, statics, out, sections, n, step, stream):
+        sums, prior = self.pools.get("sums"), self.pools.get("prior")
+        rc = self._fn(statics.data_ptr(), sums.data_ptr() if sums is not None else None, self.b.capacity, self.width,
+                      prior.data_ptr() if prior is not None else None, int(self._norm_var), int(self.state.running),
+                      *sections, n, stream)
+        _native.check(rc, "pds_multistream_cmvn")
+
+    def stats(self, ids: np.ndarray) -> np.ndarray:
+        """:func:`StreamBatch.cmvn_stats` of the checked `ids`"""
+        F = self.width
+        out = np.zeros((len(ids), 2, F + 1), dtype=np.float64)
+        if self.prior is not None:
+            out[:] = self.prior
+        live = np.flatnonzero(~self.state.fresh[ids]) if self.state.running else np.zeros(0, dtype=np.int64)
+        if len(live):
+            at = self.b._torch.from_numpy(ids[live]).to(self.b.device)
+            out[live, :, :F] = self.pools["sums"][at].cpu().numpy()
+            out[live, 0, F] = self.state.counts(ids[live])
+        return out
+
+
+class _SlidingStage(_Stage):
+    """`sliding_cmvn`, a kernel of the stages library.  Pools: ``ring``, every stream's last ``cmn_window + 1`` static
+    rows, ``(capacity, cmn_window + 1, F)`` of `dtype`, and ``sums``, float64 ``(capacity, 2, F)`` (a fresh stream's
+    are not read: no fill)"""
+
+    sections = ("sliding",)
+
+    def __init__(self, batch, spec, width):
+        super().__init__(batch, spec, width)
+        torch, dev = batch._torch, batch.device
+        self.state = SlidingState(batch.capacity, spec.cmn_window, spec.refresh)
+        self._fn = _typed(_native.stages_lib(), "pds_multistream_sliding", batch.dtype)
+        self.pools["ring"] = torch.empty((batch.capacity, self.state.ring_rows, width), dtype=batch._tdtype, device=dev)
+        self.pools["sums"] = torch.empty((batch.capacity, 2, width), dtype=torch.float64, device=dev)
+
+    def _run(self, statics, out, sections, n, step, stream):
+        spec = self.spec
+        rc = self._fn(statics.data_ptr(), self.pools["ring"].data_ptr(), self.pools["sums"].data_ptr(),
+                      self.b.capacity, self.width, spec.cmn_window, int(spec.norm_vars), spec.refresh, *sections, n,
+                      stream)
+        _native.check_stages(rc, "pds_multistream_sliding")
+
+
+class _DeltasStage(_Stage):
+    """`deltas`: `spec` is :func:`streaming_deltas`'s ``(Deltas, num_deltas, context_window)``.  Pool: ``hist``, two
+    halves of every stream's last ``2 H`` static rows, ``(2, capacity, 2 H, F)`` of `dtype`"""
+
+    sections = ("deltas", "elems")
+    counts = "rows"
+
+    def __init__(self, batch, spec, width):
+        super().__init__(batch, spec, width)
+        deltas, self._K, W = spec
+        self.state = DeltaState(batch.capacity, self._K * W)
+        self.width = (self._K + 1) * width
+        self.pools["hist"] = batch._torch.zeros((2, batch.capacity, self.state.hist_rows, width), dtype=batch._tdtype,
+                                                device=batch.device)
+        self._filts, self._filt_off = deltas._filters_on(batch.device)
+        self._fn = _typed(batch._lib, "pds_multistream_deltas", batch.dtype)
+
+    def _run(self, statics, out, sections, n, step, stream):
+        rc = self._fn(statics.data_ptr() if statics.shape[0] else None, self.pools["hist"].data_ptr(),
+                      self.b.capacity, self.state.hist_rows, self.width_in, self._filts.data_ptr(),
+                      self._filt_off.data_ptr(), self._K, *sections, n, step["elems"], out.data_ptr(), stream)
+        _native.check(rc, "pds_multistream_deltas")
+
+
+class _StackStage(_Stage):
+    """`stack`: `spec` is :func:`streaming_stack`'s ``(Stack, num_vectors, pad, fill)``; `fill` is the constant
+    rounded to `dtype`, as ``numpy.pad`` rounds it.  Pool: ``pending``, two halves of every stream's rows not yet
+    returned, ``(2, capacity, num_vectors - 1, C)`` of `dtype` (a stream without any has nothing read from its slot: no
+    fill)"""
+
+    sections = ("stack", "stack_elems")
+    counts = "groups"
+
+    def __init__(self, batch, spec, width):
+        super().__init__(batch, spec, width)
+        _, nv, self._pad, fill = spec
+        self.fill = float(batch.dtype.type(fill))
+        self.state = StackState(batch.capacity, nv, self._pad != _PAD_NONE)
+        self.width = nv * width
+        self.pools["pending"] = batch._torch.empty((2, batch.capacity, nv - 1, width), dtype=batch._tdtype,
+                                                   device=batch.device)
+        self._fn = _typed(batch._lib, "pds_multistream_stack", batch.dtype)
+
+    def _run(self, new, out, sections, n, step, stream):
+        rc = self._fn(new.data_ptr() if new.shape[0] else None, self.pools["pending"].data_ptr(), self.b.capacity,
+                      self.state.nv, self.width_in, *sections, n, step["elems"], self._pad, self.fill,
+                      out.data_ptr() if out.shape[0] else None, stream)
+        _native.check(rc, "pds_multistream_stack")
+
+
 class _TickBatch:
     """What :class:`StreamBatch` and :class:`multistream_si.SiStreamBatch` share: the constructor, the public calls, the
     pools, the pinned staging and -- :func:`_tick` -- the one pipeline of a tick, ``compute_chunks`` and ``finalize``
@@ -852,7 +1029,9 @@ class _TickBatch:
     `_wrong_computer`), :func:`_new_state` (its host state machine -- ``chunk_step``, ``commit_chunks``,
     ``finalize_step``, ``reset`` over a :class:`_StreamWords` -- and the row length of the carry pool),
     :func:`_emit_order` (which order the emitting streams launch in), `_launch_extra` (the keys of a step that follow
-    offset, length, frame count and first row in the launch metadata, a row each) and :func:`_feature_launch`."""
+    offset, length, frame count and first row in the launch metadata, a row each) and :func:`_feature_launch`.  The
+    post stages are `_stages`, :class:`_Stage` objects by name, built by the constructor in the order they run;
+    `_tick` and `close` loop over it, and `dstate`, `cstate`, `wstate` and `kstate` are the states of its members."""
 
     _computer_type = _wrong_computer = None
     _launch_extra = ()
@@ -865,9 +1044,9 @@ class _TickBatch:
         dtype = np.dtype(dtype)
         if dtype not in (np.float32, np.float64):
             raise TypeError("StreamBatch: samples must be float32 or float64")
-        spec, coeff = streaming_deltas(deltas), streaming_preemphasis(preemphasis)
-        # the computer's own width, which the feature launch writes, and the width the post stages see: the cepstral
-        # one with `cepstra` (whose bounds on the width are checked here, where it is known)
+        dspec, coeff = streaming_deltas(deltas), streaming_preemphasis(preemphasis)
+        # the width the cmvn sees is the cepstral one with `cepstra` (whose bounds on the computer's width are checked
+        # here, where it is known)
         pspec = streaming_cepstra(cepstra)
         width = computer.num_coeffs
         if pspec is not None:
@@ -881,23 +1060,17 @@ class _TickBatch:
         nspec = streaming_dither(dither)
         self.state, row_length = self._new_state(computer, capacity)
         # the device side: `computer`'s plan, the carry pool of ``2 * capacity * row_length`` samples, the
-        # previous-sample pool (with a pre-emphasis), the staging buffers, the history pool of the deltas, the pool of
-        # running sums of the cmvn and the pool of pending rows of the stack
+        # previous-sample pool (with a pre-emphasis), the staging buffers and what the post stages keep
         torch = _native.require_device()
         self._torch = torch
         self._lib = _native.lib()
         self.dtype = dtype
         self.capacity = self.state.capacity
         self.device = torch.device("cuda", torch.cuda.current_device())
-        self._F0 = computer.num_coeffs  # coefficients of the computer per row
-        self._cepstra = pspec
-        self._F = width  # statics per row, as the post stages see them
-        self._C = self._F  # ... and coefficients per row before stacking
         self._comp = computer
         self._plan = computer._native_plan(self.device)
         self._tdtype = torch.float32 if dtype == np.float32 else torch.float64
-        self._assemble = (self._lib.pds_multistream_assemble_f32 if dtype == np.float32
-                          else self._lib.pds_multistream_assemble_f64)
+        self._assemble = _typed(self._lib, "pds_multistream_assemble", dtype)
         self._tile = int(self._lib.pds_multistream_tile())
         self._row_length = int(row_length)
         self._pool = torch.zeros((2, self.capacity, self._row_length), dtype=self._tdtype, device=self.device)
@@ -919,49 +1092,26 @@ class _TickBatch:
         self._up_events = [None, None]
         self._up_next = 0
         self._down = None  # pinned features of the host-array calls
-        self.dstate = self._hist = None
-        if spec is not None:
-            self._deltas, self._K, W = spec
-            self.dstate = DeltaState(self.capacity, self._K * W)
-            self._C = (self._K + 1) * self._F
-            self._hist = torch.zeros((2, self.capacity, self.dstate.hist_rows, self._F), dtype=self._tdtype,
-                                     device=self.device)
-            self._d_filts, self._d_filt_off = self._deltas._filters_on(self.device)
-            self._deltas_fn = (self._lib.pds_multistream_deltas_f32 if dtype == np.float32
-                               else self._lib.pds_multistream_deltas_f64)
-        self.cstate = self._sums = self._d_prior = self._prior = None
+        # the post stages by name, in the order they run.  `_F0` is the computer's own width, which the feature launch
+        # writes, `_F` the statics' as the post stages see them and `_C` the one before stacking
+        self._F0, self._F = computer.num_coeffs, width
+        self._stages = {}
+        width = self._F0
         if cspec is not None:
-            self._cmvn, self._prior, self._norm_var = cspec
-            self.cstate = CmvnState(self.capacity, int(self._prior[0, -1]) if self._prior is not None else 0,
-                                    bool(cmvn_running))
-            if self._prior is not None:
-                self._d_prior = torch.from_numpy(np.ascontiguousarray(self._prior[:, :-1])).to(self.device)
-            if self.cstate.running:  # every stream's running sums (a fresh stream's slot is never read: no fill)
-                self._sums = torch.empty((self.capacity, 2, self._F), dtype=torch.float64, device=self.device)
-            self._cmvn_fn = (self._lib.pds_multistream_cmvn_f32 if dtype == np.float32
-                             else self._lib.pds_multistream_cmvn_f64)
-        self.wstate = self._ring = self._wsums = None
-        if wspec is not None:
-            self._sliding = wspec
-            self.wstate = SlidingState(self.capacity, wspec.cmn_window, wspec.refresh)
-            stages = _native.stages_lib()
-            # every stream's last cmn_window + 1 static rows and its two sums (a fresh stream's are not read: no fill)
-            self._ring = torch.empty((self.capacity, self.wstate.ring_rows, self._F), dtype=self._tdtype,
-                                     device=self.device)
-            self._wsums = torch.empty((self.capacity, 2, self._F), dtype=torch.float64, device=self.device)
-            self._sliding_fn = (stages.pds_multistream_sliding_f32 if dtype == np.float32
-                                else stages.pds_multistream_sliding_f64)
-        self.num_coeffs = self._C
-        self.kstate = self._pending = None
-        if kspec is not None:
-            self._stack, nv, self._pad, fill = kspec
-            self._fill = float(dtype.type(fill))  # (rounded to `dtype` as numpy.pad rounds it)
-            self.kstate = StackState(self.capacity, nv, self._pad != _PAD_NONE)
-            self.num_coeffs = nv * self._C
-            # every stream's pending rows (a stream without any has nothing read from its slot: no fill)
-            self._pending = torch.empty((2, self.capacity, nv - 1, self._C), dtype=self._tdtype, device=self.device)
-            self._stack_fn = (self._lib.pds_multistream_stack_f32 if dtype == np.float32
-                              else self._lib.pds_multistream_stack_f64)
+            cspec += (bool(cmvn_running),)
+        for name, kind, spec in (("cepstra", _CepstraStage, pspec), ("cmvn", _CmvnStage, cspec),
+                                 ("sliding", _SlidingStage, wspec), ("deltas", _DeltasStage, dspec),
+                                 ("stack", _StackStage, kspec)):
+            if spec is not None:
+                stage = self._stages[name] = kind(self, spec, width)
+                width = stage.width
+        self.num_coeffs = width
+        self._C = self._stages["stack"].width_in if "stack" in self._stages else width
+        states = {name: stage.state for name, stage in self._stages.items()}
+        self.cstate, self.wstate, self.dstate, self.kstate = map(states.get, ("cmvn", "sliding", "deltas", "stack"))
+        # what a tick asks of _tick_layout: a stage's sections are placed if it is there
+        self._layout_flags = (*(flag in states for flag in ("deltas", "cmvn", "stack")), self.nstate is not None,
+                              "sliding" in states)
 
     # ---- public interface -----------------------------------------------------------
 
@@ -1003,17 +1153,7 @@ class _TickBatch:
         self._check_open()
         if self.cstate is None:
             raise ValueError(f"{type(self).__name__} was built without cmvn")
-        ids = self.state.check_ids(ids)
-        F = self._F
-        out = np.zeros((len(ids), 2, F + 1), dtype=np.float64)
-        if self._prior is not None:
-            out[:] = self._prior
-        live = np.flatnonzero(~self.cstate.fresh[ids]) if self.cstate.running else np.zeros(0, dtype=np.int64)
-        if len(live):
-            at = self._torch.from_numpy(ids[live]).to(self.device)
-            out[live, :, :F] = self._sums[at].cpu().numpy()
-            out[live, 0, F] = self.cstate.counts(ids[live])
-        return out
+        return self._stages["cmvn"].stats(self.state.check_ids(ids))
 
     def compute_chunks(self, ids, chunks: Sequence) -> List[np.ndarray]:
         """``compute_chunk`` of ``chunks[i]`` (1-D host array) for stream ``ids[i]``; returns the list of feature
@@ -1065,8 +1205,9 @@ class _TickBatch:
 
     def close(self) -> None:
         """Release the pools and the pinned buffers; the object cannot be used afterwards"""
-        self._pool = self._hist = self._prev = self._sums = self._d_prior = self._pending = None
-        self._ring = self._wsums = None
+        for stage in self._stages.values():
+            stage.release()
+        self._pool = self._prev = None
         self._up = [None, None]
         self._up_events = [None, None]
         self._down = None
@@ -1157,10 +1298,7 @@ class _TickBatch:
         rows = _exclusive_cumsum(k)
         row0 = rows[:-1]
         order = self._emit_order(step, np.flatnonzero(k > 0))
-        up = _Upload(ns, _tick_layout(n, len(order), 4 + len(self._launch_extra), not final, self.dstate is not None,
-                                      self.cstate is not None, self.kstate is not None,
-                                      *((self.nstate is not None, True) if self.wstate is not None
-                                        else (True,) if self.nstate is not None else ())))
+        up = _Upload(ns, _tick_layout(n, len(order), 4 + len(self._launch_extra), not final, *self._layout_flags))
         slot, buf = self._staging(up.words)
         up.pinned = buf.numpy()
         if ns:
@@ -1184,23 +1322,9 @@ class _TickBatch:
         lm[0], lm[1], lm[2], lm[3] = off[order], span[order], k[order], row0[order]
         for r, key in enumerate(self._launch_extra, 4):
             lm[r] = step[key][order]
-        if self.dstate is not None:
-            dstep = self.dstate.step(ids, k, final=final)
-            dstep["out_rows"] = _exclusive_cumsum(dstep["rows"])
-            elems = self.dstate.fill_meta(up.host("deltas"), up.host("elems"), ids, dstep, row0,
-                                          dstep["out_rows"][:-1], self._F)
-        if self.cstate is not None:
-            cstep = self.cstate.step(ids, k, final=final)
-            self.cstate.fill_meta(up.host("cmvn"), ids, cstep, row0)
-        if self.wstate is not None:
-            wstep = self.wstate.step(ids, k, final=final)
-            self.wstate.fill_meta(up.host("sliding"), ids, wstep, row0)
-        if self.kstate is not None:  # over what the stages before it return: the statics, or the rows of the deltas
-            new = dstep["out_rows"] if self.dstate is not None else rows
-            kstep = self.kstate.step(ids, np.diff(new), final=final)
-            kstep["out_rows"] = _exclusive_cumsum(kstep["groups"])
-            kelems = self.kstate.fill_meta(up.host("stack"), up.host("stack_elems"), ids, kstep, new[:-1],
-                                           kstep["out_rows"][:-1], self._C)
+        out_rows = rows  # every stream's first row in what the tick returns: the statics', through the stages
+        for stage in self._stages.values():
+            out_rows = stage.plan(up, ids, out_rows, final)
         stream = self._torch.cuda.current_stream(self.device)
         up.device = self._send(slot, up.words, stream)
         if final:
@@ -1220,17 +1344,9 @@ class _TickBatch:
                 self.nstate.reset(ids)
             else:
                 self.nstate.commit(ids, nstep)
-        if self._cepstra is not None:
-            feats = self._cepstra.apply(feats)  # one launch on `stream`, none without rows
-        if self.cstate is not None:
-            self._cmvn_launch(feats, up.dev("cmvn"), ids, cstep, stream)
-        if self.wstate is not None:
-            self._sliding_launch(feats, up.dev("sliding"), ids, wstep, stream)
-        if self.dstate is not None:
-            feats, rows = self._delta_launch(feats, up.dev("deltas"), up.dev("elems"), ids, dstep, elems, stream)
-        if self.kstate is not None:
-            return self._stack_launch(feats, up.dev("stack"), up.dev("stack_elems"), ids, kstep, kelems, stream)
-        return feats, rows
+        for stage in self._stages.values():
+            feats = stage.launch(up, feats, ids, stream)
+        return feats, out_rows
 
     def _assemble_launch(self, samples, i16, d_meta, d_tile_prefix, n, tiles, work_len, stream, d_dither=None):
         """one pds_multistream_assemble launch: the tick's work buffer (returned) and the new carries, in the other
@@ -1255,51 +1371,6 @@ class _TickBatch:
                                 d_tile_prefix.data_ptr(), n, tiles, work.data_ptr(), stream.cuda_stream)
         _native.check(rc, "pds_multistream_assemble")
         return work
-
-    def _cmvn_launch(self, statics, d_meta, ids, cstep, stream):
-        """one pds_multistream_cmvn launch, in place over the tick's `statics` (none in a tick without new rows: no
-        stream's sums change then)"""
-        if statics.shape[0]:
-            rc = self._cmvn_fn(statics.data_ptr(), self._sums.data_ptr() if self._sums is not None else None,
-                               self.capacity, self._F, self._d_prior.data_ptr() if self._d_prior is not None else None,
-                               int(self._norm_var), int(self.cstate.running), d_meta.data_ptr(), len(ids),
-                               stream.cuda_stream)
-            _native.check(rc, "pds_multistream_cmvn")
-        self.cstate.commit(ids, cstep)
-
-    def _sliding_launch(self, statics, d_meta, ids, wstep, stream):
-        """one pds_multistream_sliding launch, in place over the tick's `statics` (none in a tick without new rows: no
-        stream's ring or sums change then)"""
-        if statics.shape[0]:
-            rc = self._sliding_fn(statics.data_ptr(), self._ring.data_ptr(), self._wsums.data_ptr(), self.capacity,
-                                  self._F, self._sliding.cmn_window, int(self._sliding.norm_vars),
-                                  self._sliding.refresh, d_meta.data_ptr(), len(ids), stream.cuda_stream)
-            _native.check_stages(rc, "pds_multistream_sliding")
-        self.wstate.commit(ids, wstep)
-
-    def _delta_launch(self, statics, d_meta, d_elem_prefix, ids, dstep, elems, stream):
-        """one pds_multistream_deltas launch over the tick's `statics`: the rows due and the next histories"""
-        rows = dstep["out_rows"]
-        out = self._torch.empty((int(rows[-1]), self._C), dtype=self._tdtype, device=self.device)
-        rc = self._deltas_fn(statics.data_ptr() if statics.shape[0] else None, self._hist.data_ptr(), self.capacity,
-                             self.dstate.hist_rows, self._F, self._d_filts.data_ptr(), self._d_filt_off.data_ptr(),
-                             self._K, d_meta.data_ptr(), d_elem_prefix.data_ptr(), len(ids), elems, out.data_ptr(),
-                             stream.cuda_stream)
-        _native.check(rc, "pds_multistream_deltas")
-        self.dstate.commit(ids, dstep)
-        return out, rows
-
-    def _stack_launch(self, new, d_meta, d_elem_prefix, ids, kstep, elems, stream):
-        """one pds_multistream_stack launch over the tick's `new` rows: the groups that are full and the next pending
-        rows"""
-        rows = kstep["out_rows"]
-        out = self._torch.empty((int(rows[-1]), self.num_coeffs), dtype=self._tdtype, device=self.device)
-        rc = self._stack_fn(new.data_ptr() if new.shape[0] else None, self._pending.data_ptr(), self.capacity,
-                            self.kstate.nv, self._C, d_meta.data_ptr(), d_elem_prefix.data_ptr(), len(ids), elems,
-                            self._pad, self._fill, out.data_ptr() if out.shape[0] else None, stream.cuda_stream)
-        _native.check(rc, "pds_multistream_stack")
-        self.kstate.commit(ids, kstep)
-        return out, rows
 
     def _to_host(self, feats, rows, started) -> List[np.ndarray]:
         """one download into pinned memory, one synchronisation, views per stream"""

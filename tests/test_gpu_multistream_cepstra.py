@@ -239,6 +239,6 @@ def test_the_upload_is_what_it_was(monkeypatch):
         assert [a[0] for a in per_kind[kind]] == [2, 1, 3]
         for a, chunks in zip(per_kind[kind], (True, True, False)):
             n, E = a[:2]
-            assert a == (n, E, 4, chunks, stages, stages, stages) and 0 <= E <= n
+            assert a == (n, E, 4, chunks, stages, stages, stages, False, False) and 0 <= E <= n
             assert real(*a)[1] == documented_words(n, E, 4, chunks, stages, stages, stages, False)
     assert per_kind["plain"][0][1] == 2  # (the two streams of the first tick emit frames)

@@ -340,7 +340,7 @@ def test_memory_and_close():
         row = max(comp._max_support - 1, comp._skip0) + 2 * comp.frame_shift
         assert sb.state.row_length == row
         assert sb._pool.numel() * sb._pool.element_size() == 2 * 16 * row * np.dtype(dtype).itemsize
-        assert sb._prev is None and sb._hist is None
+        assert sb._prev is None and "deltas" not in sb._stages
         sb.close()
         assert sb._pool is None
         for use in (lambda: sb.compute_chunks([0], [np.zeros(10, dtype)]), lambda: sb.finalize([0]),

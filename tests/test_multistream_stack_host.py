@@ -343,6 +343,7 @@ class _FakeLib:
 
     pds_multistream_assemble_f32 = pds_multistream_assemble_f64 = None
     pds_multistream_deltas_f32 = pds_multistream_deltas_f64 = None
+    pds_multistream_cmvn_f32, pds_multistream_cmvn_f64 = "cmvn_f32", "cmvn_f64"
 
     @staticmethod
     def pds_multistream_tile():
@@ -353,11 +354,16 @@ class _FakeLibWithStack(_FakeLib):
     pds_multistream_stack_f32, pds_multistream_stack_f64 = "stack_f32", "stack_f64"
 
 
-def fake_batch(monkeypatch, lib, **kwargs):
+class _FakeStagesLib:
+    pds_multistream_sliding_f32, pds_multistream_sliding_f64 = "sliding_f32", "sliding_f64"
+
+
+def fake_batch(monkeypatch, lib, torch=_FakeTorch, **kwargs):
     from pydrobert_speech_amd import multistream
 
     class Native:
-        require_device = staticmethod(lambda: _FakeTorch)
+        require_device = staticmethod(lambda: torch)
+        stages_lib = staticmethod(lambda: _FakeStagesLib)
 
     Native.lib = staticmethod(lambda: lib)
     monkeypatch.setattr(multistream, "_native", Native)
@@ -370,7 +376,7 @@ def fake_batch(monkeypatch, lib, **kwargs):
 def test_no_stack_builds_no_state_and_asks_for_no_symbol(monkeypatch):
     for stack in (None, Stack(1), {"name": "stack", "num_vectors": 1}):
         comp, sb = fake_batch(monkeypatch, _FakeLib, stack=stack)
-        assert sb.kstate is None and sb._pending is None
+        assert sb.kstate is None and "stack" not in sb._stages
         assert sb.num_vectors == 1 and sb.num_coeffs == comp.num_coeffs and sb.lookahead == 0
     with pytest.raises(AttributeError):
         fake_batch(monkeypatch, _FakeLib, stack=Stack(2))  # (a stale library is an error, not a fall-back)
@@ -382,12 +388,14 @@ def test_stack_sizes_the_pool_and_the_rows(monkeypatch):
     F = comp.num_coeffs
     assert isinstance(sb.kstate, StackState) and sb.kstate.nv == 3 and sb.kstate.pad
     assert sb.num_vectors == 3 and sb.num_coeffs == 3 * 3 * F and sb.lookahead == 4
-    assert sb._pending == ("empty", (2, 4, 2, 3 * F)) and sb._stack_fn == "stack_f64"
+    stage = sb._stages["stack"]
+    assert stage.pools == {"pending": ("empty", (2, 4, 2, 3 * F))} and stage._fn == "stack_f64"
     sb.close()
-    assert sb._pending is None
+    assert stage.pools == {}
     comp, sb = fake_batch(monkeypatch, _FakeLibWithStack, stack=Stack(2, pad_mode="constant", constant_values=0.1))
-    assert sb.num_coeffs == 2 * F and sb._pending == ("empty", (2, 4, 1, F)) and sb._stack_fn == "stack_f32"
-    assert sb._fill == float(np.float32(0.1)) != 0.1 and not sb.kstate.half.any()  # (rounded to the batch dtype)
+    stage = sb._stages["stack"]
+    assert sb.num_coeffs == 2 * F and stage.pools == {"pending": ("empty", (2, 4, 1, F))} and stage._fn == "stack_f32"
+    assert stage.fill == float(np.float32(0.1)) != 0.1 and not sb.kstate.half.any()  # (rounded to the batch dtype)
 
 
 # ---- 4. the binding and the layout ----------------------------------------------------------------------------------
