@@ -528,6 +528,13 @@ class Deltas(PostProcessor):
         B, F, K = len(row_offsets) - 1, feats.shape[1], self.num_deltas
         if out is None:
             out = torch.empty((feats.shape[0], (K + 1) * F), dtype=torch.float32, device=feats.device)
+        elif (not _is_gpu_tensor(out) or out.dtype != torch.float32 or out.device != feats.device or out.dim() != 2
+              or out.shape[0] < feats.shape[0] or out.shape[1] < (K + 1) * F
+              or (out.shape[1] and out.stride(1) != 1) or (out.shape[0] > 1 and out.stride(0) < (K + 1) * F)):
+            # (the kernel writes (K + 1) F floats at row r * stride(0) for every row of feats: anything else is out of bounds)
+            raise ValueError(
+                "out must be a 2-D float32 GPU tensor on feats' device with at least feats' rows and (K + 1) F "
+                "columns, contiguous rows (stride(1) == 1) that do not overlap (stride(0) >= (K + 1) F)")
         if B <= 0 or feats.shape[0] == 0:
             return out
         meta, nrows = _rows_meta(row_offsets, feats.device)

@@ -220,18 +220,30 @@ class Preemphasize(PreProcessor):
         return _finish(out, was_gpu, dtype, signal, in_place)
 
     def apply_packed(self, signal, offsets, lengths):
-        """Pre-emphasise every utterance of a packed GPU buffer (see ``compute_packed``)"""
+        """Pre-emphasise every utterance of a packed GPU buffer (see ``compute_packed``)
+
+        `signal`: a 1-D GPU tensor of float32 or float64; utterance b is ``signal[offsets[b] : offsets[b] +
+        lengths[b]]``.  Returns a new tensor of `signal`'s length and dtype; samples outside every utterance keep their
+        values.
+        """
         torch = _native.require_device()
         lib = _native.lib()
         if not getattr(signal, "is_cuda", False) or signal.dim() != 1:
             raise ValueError("signal must be a 1-D GPU tensor")
+        if signal.dtype not in (torch.float32, torch.float64):
+            raise ValueError("signal must be float32 or float64")
+        offs_h = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        lens_h = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        B = len(lens_h)
+        if len(offs_h) != B:
+            raise ValueError("one offset per length")
+        if B and (offs_h.min() < 0 or lens_h.min() < 0 or int((offs_h + lens_h).max()) > signal.numel()):
+            raise ValueError("the utterances lie outside signal")
         signal = signal.contiguous()
-        offs = torch.as_tensor(np.asarray(offsets, dtype=np.int64)).to(signal.device)
-        lens_h = np.asarray(lengths, dtype=np.int64)
+        offs = torch.as_tensor(offs_h).to(signal.device)
         lens = torch.as_tensor(lens_h).to(signal.device)
         out = signal.clone()  # gaps between utterances keep their contents
         fn = lib.pds_preemphasize_f32 if signal.dtype == torch.float32 else lib.pds_preemphasize_f64
-        B = len(lens_h)
         with torch.cuda.device(signal.device):
             for lo in range(0, B, 65535):
                 hi = min(B, lo + 65535)

@@ -16,16 +16,23 @@ def test_deltas_match_reference_outputs(golden_post):
                 got = Deltas(nd, context_window=W, target_axis=1).apply(x, axis=0)
                 want = golden_post[f"deltas/out/T{T}/n{nd}/w{W}"]
                 assert got.dtype == want.dtype and got.shape == want.shape
-                assert np.allclose(got, want, rtol=1e-6, atol=1e-6)
+                if (T, nd, W) == (1, 2, 3):
+                    # the one golden that numpy.correlate (the reference, post.py:477) summed in another order than
+                    # the kernel's j-ascending one: nine taps on a one-frame, constant signal, whose exact sum is 0 --
+                    # the two orders leave residues of 0 and 3.4e-17 (tests/test_exact_post.py holds the oracle, which
+                    # the kernel equals to the bit, to that order)
+                    assert np.allclose(got, want, rtol=1e-6, atol=1e-6)
+                else:
+                    assert np.array_equal(got, want), (T, nd, W)
     x = golden_post["deltas/in/nd3"]
     got = Deltas(2, concatenate=False, target_axis=0).apply(x, axis=1)
     assert got.dtype == np.float64
-    assert np.allclose(got, golden_post["deltas/out/nd3/axis1_stack0"], rtol=1e-12, atol=1e-12)
+    assert np.array_equal(got, golden_post["deltas/out/nd3/axis1_stack0"])
     got = Deltas(1, target_axis=1).apply(x, axis=2)
-    assert np.allclose(got, golden_post["deltas/out/nd3/axis2_cat1"], rtol=1e-12, atol=1e-12)
+    assert np.array_equal(got, golden_post["deltas/out/nd3/axis2_cat1"])
     xr = x[:, :, :1].repeat(3, 2)[:4]
     got = Deltas(2, target_axis=-1, pad_mode="reflect").apply(xr, axis=1)
-    assert np.allclose(got, golden_post["deltas/out/nd3/axis0_reflect"], rtol=1e-12, atol=1e-12)
+    assert np.array_equal(got, golden_post["deltas/out/nd3/axis0_reflect"])
 
 
 @pytest.mark.parametrize("concatenate", [True, False])
@@ -55,7 +62,8 @@ def test_deltas_vs_oracle(dtype, window, num_deltas):
         buff = (rng.random(shape) * 100).astype(dtype)
         got = Deltas(num_deltas, context_window=window, target_axis=1).apply(buff, axis=0)
         want = orc.deltas(buff, axis=0, num_deltas=num_deltas, context_window=window, target_axis=1)
-        assert got.dtype == want.dtype and np.allclose(got, want)
+        # (the oracle is the kernel's arithmetic: float64, taps in ascending order, product and sum rounded separately)
+        assert got.dtype == want.dtype and np.array_equal(got, want)
 
 
 def test_cmvn_matches_reference_outputs(golden_post):
