@@ -97,6 +97,89 @@ int32_t pds_multistream_sliding_f64(double *d_statics, double *d_ring, double *d
                                     int32_t coeffs, int32_t cmn_window, int32_t norm_vars, int32_t refresh,
                                     const int64_t *d_meta, int32_t n, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * Windowed-sinc rate conversion: Kaldi's LinearResample with its feature-extraction defaults; pre.Resample.
+ *
+ * The definition.  from_rate and to_rate are positive integers, num_zeros >= 1, 0 < rolloff <= 1.
+ *
+ *     g = gcd(from_rate, to_rate);  in_unit = from_rate / g;  out_unit = to_rate / g
+ *     cutoff = rolloff * 0.5 * min(from_rate, to_rate);  width = num_zeros / (2 * cutoff)
+ *     for phase p in [0, out_unit):  t = p / to_rate
+ *         first[p] = ceil((t - width) * from_rate);  last[p] = floor((t + width) * from_rate)
+ *         ntaps[p] = last[p] - first[p] + 1
+ *         for j in [0, ntaps[p]):  d = (first[p] + j) / from_rate - t
+ *             w[p][j] = f(d) * h(d) / from_rate
+ *             f(d) = sin(2 pi cutoff d) / (pi d), and 2 cutoff at d == 0
+ *             h(d) = 0.5 (1 + cos(2 pi cutoff / num_zeros d)) for |d| < width, else 0
+ *
+ * The table is built on the host in float64: first and ntaps as int32, w as float64 padded with zeros to max_taps,
+ * the largest ntaps[p].  An utterance of n samples gives m = ceil(n * to_rate / from_rate) output samples (Kaldi's
+ * flush form), and output k = u * out_unit + p, 0 <= p < out_unit, is
+ *
+ *     y[k] = sum over j in [0, ntaps[p]) of w[p][j] * x[first[p] + u * in_unit + j]
+ *
+ * in float64, over j in ascending order, starting from +0.0, with x widened first and each product and each sum
+ * rounded separately; a tap whose index falls outside [0, n) contributes nothing; y[k] is rounded once to the output
+ * type: float32 for float32 and int16 input (int16 is widened exactly), float64 for float64 input.  NaN and infinite
+ * samples reach exactly the outputs whose windows hold them.
+ *
+ * The tables of a call: d_first and d_ntaps, int32[out_unit]; d_weights, double[max_taps][out_unit] -- tap-major, the
+ * transpose of w above, so that adjacent lanes, which own adjacent phases, read adjacent weights.  A table of more than
+ * out_unit * max_taps = 1048576 entries is refused (PDS_STAGES_ERR_INVALID): indices into it are 32-bit.
+ *
+ * The offline call, over a packed ragged batch: utterance b is the d_in_len[b] samples from d_in + d_in_off[b] on
+ * (any offset: no alignment is assumed), and its m_b outputs go to d_out + d_out_off[b].  One lane computes one output
+ * sample, adjacent lanes adjacent outputs of one utterance; max_len is the largest d_in_len[b] (it sizes the grid: an
+ * utterance's outputs beyond ceil(max_len * out_unit / in_unit) are not written).  d_out must not overlap d_in.
+ * B == 0 or max_len == 0 returns 0 without looking at the pointers; bad sizes and null pointers return
+ * PDS_STAGES_ERR_INVALID before any HIP call, as does a batch whose B * ceil(max_out / 256) blocks exceed 2^31 - 1
+ * (split the batch).
+ * --------------------------------------------------------------------------------- */
+int32_t pds_resample_packed_f32(const float *d_in, const int64_t *d_in_off, const int64_t *d_in_len,
+                                const int64_t *d_out_off, int32_t B, int64_t max_len, int32_t in_unit,
+                                int32_t out_unit, int32_t max_taps, const int32_t *d_first, const int32_t *d_ntaps,
+                                const double *d_weights, float *d_out, void *stream);
+int32_t pds_resample_packed_f64(const double *d_in, const int64_t *d_in_off, const int64_t *d_in_len,
+                                const int64_t *d_out_off, int32_t B, int64_t max_len, int32_t in_unit,
+                                int32_t out_unit, int32_t max_taps, const int32_t *d_first, const int32_t *d_ntaps,
+                                const double *d_weights, double *d_out, void *stream);
+int32_t pds_resample_packed_i16_f32(const int16_t *d_in, const int64_t *d_in_off, const int64_t *d_in_len,
+                                    const int64_t *d_out_off, int32_t B, int64_t max_len, int32_t in_unit,
+                                    int32_t out_unit, int32_t max_taps, const int32_t *d_first,
+                                    const int32_t *d_ntaps, const double *d_weights, float *d_out, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * The same conversion per stream across the ticks of batched streaming (multistream_resample.ResampleBatch).  After a
+ * stream has been given n samples in all, the due outputs are those k with
+ * first[p] + u * in_unit + ntaps[p] - 1 <= n - 1: the outputs whose whole window has arrived (the last index is
+ * non-decreasing in k, so this is a count); at the stream's end the rest up to ceil(n * to_rate / from_rate) follow,
+ * with the missing future read as nothing.  Per stream the device keeps its last max_taps - 1 input samples,
+ * d_hist = T[capacity][max_taps - 1] in the chunks' type: slot i holds sample n - (max_taps - 1) + i of a stream that
+ * has seen n samples (slots of samples below 0 are never read).  The call runs once per tick, one block per entry;
+ * d_meta holds n entries of 8 int64:
+ *   [0] stream s (0 <= s < capacity)   [1] offset of the stream's chunk in d_samples   [2] its length c (may be 0)
+ *   [3] samples n0 the stream has seen before this call (0 if fresh: the history is not read)
+ *   [4] the first output k0 to compute   [5] their number (may be 0)   [6] offset of these outputs in d_out
+ *   [7] reserved, 0
+ * and outputs k0 .. k0 + [5] - 1 are computed by the definition above over the stream's samples [0, n0 + c), bit for
+ * bit what the offline call gives over the stream's whole signal when the host follows the rule above.  An entry with
+ * c > 0 then writes the stream's next history.  Streams of one call are distinct.  d_samples and d_out may be NULL
+ * when no entry has samples or outputs.  n == 0 returns 0 without looking at the pointers; bad sizes and null pointers
+ * return PDS_STAGES_ERR_INVALID before any HIP call.
+ * --------------------------------------------------------------------------------- */
+int32_t pds_multistream_resample_f32(const float *d_samples, float *d_hist, int64_t capacity, int32_t in_unit,
+                                     int32_t out_unit, int32_t max_taps, const int32_t *d_first,
+                                     const int32_t *d_ntaps, const double *d_weights, const int64_t *d_meta, int32_t n,
+                                     float *d_out, void *stream);
+int32_t pds_multistream_resample_f64(const double *d_samples, double *d_hist, int64_t capacity, int32_t in_unit,
+                                     int32_t out_unit, int32_t max_taps, const int32_t *d_first,
+                                     const int32_t *d_ntaps, const double *d_weights, const int64_t *d_meta, int32_t n,
+                                     double *d_out, void *stream);
+int32_t pds_multistream_resample_i16_f32(const int16_t *d_samples, int16_t *d_hist, int64_t capacity, int32_t in_unit,
+                                         int32_t out_unit, int32_t max_taps, const int32_t *d_first,
+                                         const int32_t *d_ntaps, const double *d_weights, const int64_t *d_meta,
+                                         int32_t n, float *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

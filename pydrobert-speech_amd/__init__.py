@@ -20,12 +20,13 @@ from . import si  # noqa: F401  (registers the "si" computer with the FrameCompu
 from . import feed  # noqa: F401
 from . import multistream  # noqa: F401
 from . import multistream_si  # noqa: F401
+from . import multistream_resample  # noqa: F401
 
 # the reference keeps both computers in one module (compute.py:613, 996)
 compute.ShortIntegrationFrameComputer = si.ShortIntegrationFrameComputer
 compute.SIFrameComputer = si.SIFrameComputer
 from ._native import LIB_PATH, NativeError  # noqa: F401
 
-__all__ = ["alias", "compute", "config", "feed", "filters", "multistream", "multistream_si", "post", "pre", "scales", "si", "util"]
+__all__ = ["alias", "compute", "config", "feed", "filters", "multistream", "multistream_resample", "multistream_si", "post", "pre", "scales", "si", "util"]
 # ``pydrobert_speech_amd.torch`` (nn.Module faces) and ``.command_line`` import torch: on demand
 __version__ = "0.1.0"

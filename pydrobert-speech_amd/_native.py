@@ -236,6 +236,16 @@ _SLIDING_ROWS_ARGS = [
 ]
 _MS_SLIDING_ARGS = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,
                     c_void_p]
+_RESAMPLE_PACKED_ARGS = [
+    c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64,  # d_in, d_in_off, d_in_len, d_out_off, B, max_len
+    c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,  # in_unit, out_unit, max_taps, d_first, d_ntaps, d_weights
+    c_void_p, c_void_p,  # d_out, stream
+]
+_MS_RESAMPLE_ARGS = [
+    c_void_p, c_void_p, c_int64,  # d_samples, d_hist, capacity
+    c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,  # in_unit, out_unit, max_taps, d_first, d_ntaps, d_weights
+    c_void_p, c_int32, c_void_p, c_void_p,  # d_meta, n, d_out, stream
+]
 
 # name -> (restype, argtypes); every symbol include/pds_amd_stages.h declares
 STAGES_SIGNATURES = {
@@ -245,6 +255,12 @@ STAGES_SIGNATURES = {
     "pds_sliding_cmvn_rows_f64": (c_int32, _SLIDING_ROWS_ARGS),
     "pds_multistream_sliding_f32": (c_int32, _MS_SLIDING_ARGS),
     "pds_multistream_sliding_f64": (c_int32, _MS_SLIDING_ARGS),
+    "pds_resample_packed_f32": (c_int32, _RESAMPLE_PACKED_ARGS),
+    "pds_resample_packed_f64": (c_int32, _RESAMPLE_PACKED_ARGS),
+    "pds_resample_packed_i16_f32": (c_int32, _RESAMPLE_PACKED_ARGS),
+    "pds_multistream_resample_f32": (c_int32, _MS_RESAMPLE_ARGS),
+    "pds_multistream_resample_f64": (c_int32, _MS_RESAMPLE_ARGS),
+    "pds_multistream_resample_i16_f32": (c_int32, _MS_RESAMPLE_ARGS),
 }
 
 _lib = None

@@ -14,8 +14,9 @@ Same command line and on-disk result as the reference's tool -- a text map of
   device work), and on a corpus of a thousand utterances the ring's pinned buffers cost more to set
   up than they save (tools/driver_rate.py: 0.6-0.9 s without, 1.4-2.1 s with);
 * a batch of utterances (``--batch-utts`` / ``--batch-samples``) is packed into one device
-  buffer and goes through ONE launch per stage: dither, pre-emphasis (fused into the frame
-  loader when it is the last pre-processor), the fused STFT/filter-bank kernel, then each
+  buffer and goes through ONE launch per stage: rate conversion (``--preprocess '[{"name": "resample",
+  "from_rate": 8000, "to_rate": 16000}, "preemphasis"]'``: the stages behind it see the resampled batch), dither,
+  pre-emphasis (fused into the frame loader when it is the last pre-processor), the fused STFT/filter-bank kernel, then each
   post-processor over the packed rows (a ``Cepstra`` -- ``--postprocess '[{"name": "mfcc", "num_ceps": 13}]'`` --
   works row by row, so the whole batch is one call and one launch, and the row offsets stay as they are; a
   ``SlidingCMVN`` -- ``{"name": "sliding_cmvn", "cmn_window": 600}`` -- normalises every utterance by itself in one
@@ -41,7 +42,7 @@ import numpy as np
 from .alias import alias_factory_subclass_from_arg
 from .compute import FrameComputer
 from .post import Cepstra, Deltas, PostProcessor, SlidingCMVN, Stack, Standardize
-from .pre import Dither, Preemphasize, PreProcessor
+from .pre import Dither, Preemphasize, PreProcessor, Resample
 from .util import SIGNAL_SOURCES, read_signal
 
 __all__ = ["FeatureDirWriter", "signals_to_torch_feat_dir"]
@@ -113,7 +114,7 @@ class FeatureDirWriter:
                  force_as: Optional[str] = None, seed: int = 0, file_prefix: str = "",
                  file_suffix: str = ".pt", manifest=None, precision: str = "float32", staging_ring: bool = False):
         for pre in preprocessors:
-            if not isinstance(pre, (Dither, Preemphasize)):
+            if not isinstance(pre, (Dither, Preemphasize, Resample)):
                 raise NotImplementedError(f"pre-processor {type(pre).__name__}")
         self.computer, self.pre, self.post = computer, list(preprocessors), list(postprocessors)
         self.out_dir, self.channel, self.force_as, self.seed = out_dir, channel, force_as, seed
@@ -161,7 +162,7 @@ class FeatureDirWriter:
             return through_feed
         host = np.concatenate(signals) if offsets[-1] else np.zeros(0, self.dtype)
         packed = torch.from_numpy(host).to("cuda")
-        if packed.dtype == torch.int16 and not (self.pre and isinstance(self.pre[0], Dither)):
+        if packed.dtype == torch.int16 and not (self.pre and isinstance(self.pre[0], (Dither, Resample))):
             packed = packed.to(torch.float32)  # (uploaded as PCM, widened on the device)
         fused = 0.0
         for k, pre in enumerate(self.pre):
@@ -170,6 +171,11 @@ class FeatureDirWriter:
                 # int16 is widened by the dither's own load)
                 seeds = [self.seed + first_index + b for b in range(len(signals))]
                 packed = pre.apply_packed(packed, offsets[:-1], lengths, seeds=seeds)
+            elif isinstance(pre, Resample):
+                # the one stage that changes the lengths: the stages behind it get the new offsets and lengths (PCM
+                # that is still int16 is widened by the resampler's own load)
+                packed, starts, lengths = pre.apply_packed(packed, offsets[:-1], lengths)
+                offsets = np.concatenate([starts, [packed.numel()]]).astype(np.int64)
             elif k == len(self.pre) - 1 and getattr(self.computer, "fuses_preemphasis", False):
                 fused = pre.coeff  # rides along with the frame loads (STFT computers only)
             else:

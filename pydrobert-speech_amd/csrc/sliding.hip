@@ -8,17 +8,19 @@
 
 #include "../../include/pds_amd_stages.h"
 #include "sliding_window.h"
+#include "stages_internal.h"
 
 namespace pds {
 
 static thread_local std::string g_stages_error;
 
-static int32_t stages_invalid(const char *msg) {
+// (shared with resample.hip through stages_internal.h: one error string for the whole library)
+int32_t stages_invalid(const char *msg) {
   g_stages_error = msg;
   return PDS_STAGES_ERR_INVALID;
 }
 
-static int32_t stages_hip_fail(hipError_t err, const char *what) {
+int32_t stages_hip_fail(hipError_t err, const char *what) {
   g_stages_error = std::string(what) + ": " + hipGetErrorString(err);
   return PDS_STAGES_ERR_HIP;
 }
