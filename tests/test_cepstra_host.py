@@ -138,3 +138,33 @@ def test_c_entry_points_validate_arguments_without_a_device(name):
     assert fn(null, 40, 0, 40, null, 13, 0, null, 13, null) == 0
     assert fn(null, 256, 0, 255, null, 255, 1, null, 256, null) == 0
     refused(b"F / K", null, 40, 0, 0, null, 13, 0, null, 13, null)
+
+
+def test_the_staging_index_of_the_kernel_is_an_exact_integer_division():
+    """``cepstra_rows_kernel`` fills its tile through ``lr = (unsigned)(((float)e + 0.5f) * rcpf(wd))`` and takes that
+    for ``e / wd``: word e of a block's ``rows * wd`` staged words, ``wd`` = ``W`` 32-bit words per float32 row and
+    ``2 W`` per float64 row, ``W <= 256``, at most 64 rows per block.  Swept here in float32 as the device computes it
+    (``e + 0.5`` is exact below 2^23; one rounding of the product; truncation), for every ``wd`` in 1..512, every ``e``
+    in ``[0, 64 wd)`` and every reciprocal within 2 ulp of the correctly rounded one -- the hardware's is specified
+    to about 1 ulp."""
+    checked = 0
+    for wd in range(1, 513):
+        e = np.arange(64 * wd, dtype=np.int64)
+        half = e.astype(np.float32) + np.float32(0.5)
+        assert half.dtype == np.float32 and (half.astype(np.float64) == e + 0.5).all()
+        exact = np.float32(1.0) / np.float32(wd)  # (IEEE division: correctly rounded)
+        assert exact.dtype == np.float32
+        invs, lo, hi = [exact], exact, exact
+        for _ in range(2):
+            lo, hi = np.nextafter(lo, np.float32(0.0)), np.nextafter(hi, np.float32(2.0))
+            invs += [lo, hi]
+        assert len({float(v) for v in invs}) == 5 and all(v.dtype == np.float32 for v in invs)
+        want = e // wd
+        for inv in invs:
+            prod = half * inv
+            assert prod.dtype == np.float32
+            lr = np.trunc(prod).astype(np.int64)
+            bad = np.flatnonzero(lr != want)
+            assert bad.size == 0, (wd, float(inv), int(bad[0]), int(lr[bad[0]]), int(want[bad[0]]))
+            checked += len(e)
+    assert checked == 5 * 64 * (512 * 513 // 2)
