@@ -180,6 +180,65 @@ int32_t pds_multistream_resample_i16_f32(const int16_t *d_samples, int16_t *d_hi
                                          const int32_t *d_ntaps, const double *d_weights, const int64_t *d_meta,
                                          int32_t n, float *d_out, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * Energy VAD: Kaldi's voiced-frame decision (compute-vad-energy, ComputeVadEnergy); post.EnergyVAD.  Library
+ * version 101 on.
+ *
+ * The definition.  For an utterance of T >= 1 frames with log energies e_t, each widened to float64 first,
+ * energy_mean_scale >= 0, frames_context >= 0, 0 < proportion_threshold < 1:
+ *
+ *     if energy_mean_scale != 0:
+ *         p_j = sum of e_t over t = j, j + 64, j + 128, .. in that order, starting from +0.0      (0 <= j < 64)
+ *         s   = +0.0;  for j = 0 .. 63 in order:  s += p_j
+ *         thr = energy_threshold + (energy_mean_scale * s) / T       (each operation rounded once, in float64)
+ *     else:
+ *         thr = energy_threshold                                      (the energies are not summed)
+ *     for frame t:  lo = max(0, t - frames_context);  hi = min(T - 1, t + frames_context)
+ *         den = hi - lo + 1;  num = the number of u in [lo, hi] with e_u > thr
+ *         voiced_t = (double) num >= (double) den * proportion_threshold
+ *
+ * The 64 interleaved partial sums are part of the result (in its last bits): lane j of a wave owns p_j, and the host
+ * reproduces the sum.  A NaN energy is never above the threshold; a NaN or infinite sum makes every comparison false
+ * or true as IEEE says; nothing is special-cased.  csrc/vad_rule.h holds the rule for host and device.
+ *
+ * The call, over a packed ragged batch: utterance b is the d_nrows[b] rows from row d_row_off[b] on; d_energy points
+ * at the energy of row 0 and the energy of row r lies r * stride elements behind it (stride >= 1: the row stride of
+ * the feature matrix whose column this is).  d_voiced[r] becomes 0 or 1 for every row r of every utterance -- rows of
+ * no utterance are not written -- and d_count[b] the number of voiced rows of utterance b (0 for an empty one).  One
+ * wave handles one utterance.  max_rows is the largest d_nrows[b]; it only tells a batch without rows.  B == 0 or
+ * max_rows == 0 returns 0 without looking at the pointers (nothing is written then, d_count included); bad sizes,
+ * parameters outside the ranges above and null pointers return PDS_STAGES_ERR_INVALID before any HIP call.
+ * --------------------------------------------------------------------------------- */
+int32_t pds_vad_energy_rows_f32(const float *d_energy, int64_t stride, const int64_t *d_row_off,
+                                const int64_t *d_nrows, int32_t B, int64_t max_rows, double energy_threshold,
+                                double energy_mean_scale, int32_t frames_context, double proportion_threshold,
+                                uint8_t *d_voiced, int64_t *d_count, void *stream);
+int32_t pds_vad_energy_rows_f64(const double *d_energy, int64_t stride, const int64_t *d_row_off,
+                                const int64_t *d_nrows, int32_t B, int64_t max_rows, double energy_threshold,
+                                double energy_mean_scale, int32_t frames_context, double proportion_threshold,
+                                uint8_t *d_voiced, int64_t *d_count, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * Selection of the kept rows of a packed ragged batch, in order (Kaldi's select-voiced-frames); post.EnergyVAD.
+ *
+ * Rows are `words` 32-bit words wide and are copied as they are, byte for byte (NaN payloads and signed zeros pass):
+ * a float32 row of C values has C words, a float64 row 2 C.  in_stride and out_stride, the distances from row to
+ * row, are in 32-bit words too (both >= words).  Utterance b is the d_nrows[b] rows from row d_row_off[b] of d_in on,
+ * d_keep[r] belongs to row r of d_in, and the rows of utterance b whose d_keep is not 0 are written, in order, to
+ * rows d_out_row_off[b], d_out_row_off[b] + 1, .. of d_out; nothing else of d_out is written.  The caller sizes d_out
+ * and lays out d_out_row_off from the counts of kept rows (those of the decision call above, for its d_voiced).
+ * d_out must not overlap d_in.
+ *
+ * One block handles one (utterance, tile of 256 rows): it counts the kept rows in front of its tile, ranks its own by
+ * ballots, and all its lanes copy the kept rows, adjacent lanes adjacent words; max_rows is the largest d_nrows[b] (it
+ * sizes the grid; an utterance's rows beyond it are not looked at).  B == 0 or max_rows == 0 returns 0 without
+ * looking at the pointers; bad sizes, strides and null pointers return PDS_STAGES_ERR_INVALID before any HIP call, as
+ * does a batch whose B * ceil(max_rows / 256) blocks exceed 2^31 - 1 (split the batch).
+ * --------------------------------------------------------------------------------- */
+int32_t pds_select_rows_w32(const void *d_in, int64_t in_stride, int32_t words, const int64_t *d_row_off,
+                            const int64_t *d_nrows, int32_t B, int64_t max_rows, const uint8_t *d_keep,
+                            const int64_t *d_out_row_off, void *d_out, int64_t out_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,6 +246,15 @@ _MS_RESAMPLE_ARGS = [
     c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,  # in_unit, out_unit, max_taps, d_first, d_ntaps, d_weights
     c_void_p, c_int32, c_void_p, c_void_p,  # d_meta, n, d_out, stream
 ]
+_VAD_ENERGY_ARGS = [
+    c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64,  # d_energy, stride, d_row_off, d_nrows, B, max_rows
+    c_double, c_double, c_int32, c_double,  # energy_threshold, energy_mean_scale, frames_context, proportion_threshold
+    c_void_p, c_void_p, c_void_p,  # d_voiced, d_count, stream
+]
+_SELECT_ROWS_ARGS = [
+    c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int64,  # d_in, in_stride, words, d_row_off, d_nrows, B, max_rows
+    c_void_p, c_void_p, c_void_p, c_int64, c_void_p,  # d_keep, d_out_row_off, d_out, out_stride, stream
+]
 
 # name -> (restype, argtypes); every symbol include/pds_amd_stages.h declares
 STAGES_SIGNATURES = {
@@ -261,6 +270,9 @@ STAGES_SIGNATURES = {
     "pds_multistream_resample_f32": (c_int32, _MS_RESAMPLE_ARGS),
     "pds_multistream_resample_f64": (c_int32, _MS_RESAMPLE_ARGS),
     "pds_multistream_resample_i16_f32": (c_int32, _MS_RESAMPLE_ARGS),
+    "pds_vad_energy_rows_f32": (c_int32, _VAD_ENERGY_ARGS),
+    "pds_vad_energy_rows_f64": (c_int32, _VAD_ENERGY_ARGS),
+    "pds_select_rows_w32": (c_int32, _SELECT_ROWS_ARGS),
 }
 
 _lib = None

@@ -20,7 +20,12 @@ Same command line and on-disk result as the reference's tool -- a text map of
   post-processor over the packed rows (a ``Cepstra`` -- ``--postprocess '[{"name": "mfcc", "num_ceps": 13}]'`` --
   works row by row, so the whole batch is one call and one launch, and the row offsets stay as they are; a
   ``SlidingCMVN`` -- ``{"name": "sliding_cmvn", "cmn_window": 600}`` -- normalises every utterance by itself in one
-  launch over the packed rows, ``SlidingCMVN.apply_rows``);
+  launch over the packed rows, ``SlidingCMVN.apply_rows``; an ``EnergyVAD`` -- ``{"name": "vad"}`` -- decides and
+  drops the unvoiced rows of every utterance on the device, ``EnergyVAD.apply_rows``, and the stages behind it see
+  the shorter utterances; with ``"select_last": true`` it decides where it stands, the later stages see all frames
+  and the rows are dropped after the last stage -- Kaldi's order, ``[{"name": "mfcc", "energy": true}, {"name":
+  "vad", "select_last": true}, {"name": "sliding_cmvn"}]`` -- during which no later stage may change an utterance's
+  row count and no second selection may wait; an utterance without a voiced frame is written as a ``(0, F)`` tensor);
 * features come back in one transfer per batch and are written with ``torch.save``.
 
 Differences from the reference, by design: arithmetic is float32 unless ``--precision
@@ -41,7 +46,7 @@ import numpy as np
 
 from .alias import alias_factory_subclass_from_arg
 from .compute import FrameComputer
-from .post import Cepstra, Deltas, PostProcessor, SlidingCMVN, Stack, Standardize
+from .post import Cepstra, Deltas, EnergyVAD, PostProcessor, SlidingCMVN, Stack, Standardize
 from .pre import Dither, Preemphasize, PreProcessor, Resample
 from .util import SIGNAL_SOURCES, read_signal
 
@@ -219,7 +224,9 @@ class FeatureDirWriter:
                 feed.close()
             # room for what the post-processors make of a row (Deltas: (K + 1) C columns): tried on a few zero rows
             try:
-                probe, _ = self._postprocess(torch.randn((64, C), device="cuda"), np.asarray([0, 64], dtype=np.int64))
+                # (a selection keeps all rows of the probe: it can only shrink what comes back, 0 rows included)
+                probe, _ = self._postprocess(torch.randn((64, C), device="cuda"), np.asarray([0, 64], dtype=np.int64),
+                                             probe=True)
                 widen = -(-probe.numel() // (64 * C))
             except Exception:  # (a post-processor that wants more rows than the probe has)
                 widen = 4
@@ -239,36 +246,75 @@ class FeatureDirWriter:
         rows = out_rows["rows"] if self.post else own_rows
         return [feats[rows[b] : rows[b + 1]].clone() for b in range(len(signals))]
 
-    def _postprocess(self, feats, rows):
+    def _postprocess(self, feats, rows, probe=False):
+        """`feats`, `rows` through the post-processors in order.  `probe`: a selection keeps every row (the widest
+        result the chain can give: what sizes a buffer)"""
         import torch
 
+        pending = None  # (the EnergyVAD with select_last, its mask, the row offsets the mask goes with)
         for post in self.post:
-            if isinstance(post, Stack) and post.time_axis in (0, -2) and feats.dtype == torch.float32:
-                try:
-                    feats, rows = post.apply_rows(feats, rows)
-                    continue
-                except ValueError:
-                    pass  # a pad mode the row kernel does not have: per utterance below
-            elif isinstance(post, Cepstra):
-                feats = post.apply(feats, axis=-1)  # row by row: the whole packed batch in one launch, same rows
+            if isinstance(post, EnergyVAD) and post.select_last and not probe:
+                # decided here, on the rows as they are here; the later stages see all frames
+                if pending is not None:
+                    raise ValueError(
+                        f"two {type(post).__name__} stages with select_last: the selection of the first is still "
+                        "pending where the second stands")
+                voiced, _ = post.decide_rows(self._vad_rows(feats), rows)
+                pending = (post, voiced, rows)
                 continue
-            elif isinstance(post, SlidingCMVN) and feats.dtype in (torch.float32, torch.float64):
-                feats = post.apply_rows(feats, rows)  # every utterance by itself, the packed batch in one launch
-                continue
-            elif isinstance(post, Standardize) and post.have_stats:
-                feats = post.apply(feats, axis=-1)  # one global transform: the whole batch at once
-                continue
-            elif isinstance(post, Standardize) and feats.dtype == torch.float32 and feats.shape[0]:
-                # (an utterance of fewer than two rows is an error of Standardize, raised below)
-                if all(rows[b + 1] - rows[b] >= 2 for b in range(len(rows) - 1)):
-                    feats = post.apply_rows(feats, rows)
-                    continue
-            # any other post-processor (Deltas acts along axis -1 here, exactly as the reference's
-            # tool calls it): utterance by utterance on the device
-            pieces = [post.apply(feats[rows[b] : rows[b + 1]]) for b in range(len(rows) - 1)]
-            rows = np.concatenate([[0], np.cumsum([p.shape[0] for p in pieces])]).astype(np.int64)
-            feats = torch.cat(pieces) if pieces else feats
+            before = rows
+            feats, rows = self._postprocess_one(post, feats, rows, probe)
+            if pending is not None:
+                if not np.array_equal(np.diff(rows), np.diff(before)):
+                    raise ValueError(
+                        f"{type(post).__name__} changes the utterances' row counts behind {type(pending[0]).__name__} "
+                        "with select_last, whose decisions go with the rows as they were there")
+                if not np.array_equal(rows, pending[2]):
+                    # (the same counts at other offsets: the mask moves with the utterances)
+                    mask, old = pending[1], pending[2]
+                    moved = torch.zeros((feats.shape[0],), dtype=mask.dtype, device=mask.device)
+                    for b in range(len(rows) - 1):
+                        moved[rows[b] : rows[b + 1]] = mask[old[b] : old[b + 1]]
+                    pending = (pending[0], moved, rows)
+        if pending is not None:  # behind the last stage: the rows are dropped
+            feats, rows = pending[0].select_rows(self._vad_rows(feats), rows, pending[1])
         return feats, rows
+
+    @staticmethod
+    def _vad_rows(feats):
+        import torch
+
+        return feats if feats.dtype in (torch.float32, torch.float64) else feats.to(torch.float64)
+
+    def _postprocess_one(self, post, feats, rows, probe):
+        """one post-processor over the packed rows: ``(feats, rows)``"""
+        import torch
+
+        if isinstance(post, EnergyVAD):
+            if probe:
+                return feats, rows
+            # decided and dropped where it stands: the stages behind it see the shorter utterances
+            return post.apply_rows(self._vad_rows(feats), rows)
+        if isinstance(post, Stack) and post.time_axis in (0, -2) and feats.dtype == torch.float32:
+            try:
+                return post.apply_rows(feats, rows)
+            except ValueError:
+                pass  # a pad mode the row kernel does not have: per utterance below
+        elif isinstance(post, Cepstra):
+            return post.apply(feats, axis=-1), rows  # row by row: the whole packed batch in one launch, same rows
+        elif isinstance(post, SlidingCMVN) and feats.dtype in (torch.float32, torch.float64):
+            return post.apply_rows(feats, rows), rows  # every utterance by itself, the packed batch in one launch
+        elif isinstance(post, Standardize) and post.have_stats:
+            return post.apply(feats, axis=-1), rows  # one global transform: the whole batch at once
+        elif isinstance(post, Standardize) and feats.dtype == torch.float32 and feats.shape[0]:
+            # (an utterance of fewer than two rows is an error of Standardize, raised below)
+            if all(rows[b + 1] - rows[b] >= 2 for b in range(len(rows) - 1)):
+                return post.apply_rows(feats, rows), rows
+        # any other post-processor (Deltas acts along axis -1 here, exactly as the reference's
+        # tool calls it): utterance by utterance on the device
+        pieces = [post.apply(feats[rows[b] : rows[b + 1]]) for b in range(len(rows) - 1)]
+        rows = np.concatenate([[0], np.cumsum([p.shape[0] for p in pieces])]).astype(np.int64)
+        return (torch.cat(pieces) if pieces else feats), rows
 
     # -- the loop -------------------------------------------------------------------------------
 

@@ -225,7 +225,7 @@ static int32_t launch_ms_sliding(T *d_statics, T *d_ring, double *d_sums, int64_
 
 extern "C" {
 
-int32_t pds_stages_version(void) { return 100; }
+int32_t pds_stages_version(void) { return 101; }  // 101: the energy VAD (vad.hip)
 
 const char *pds_stages_last_error(void) { return pds::g_stages_error.c_str(); }
 

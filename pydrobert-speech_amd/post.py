@@ -1,4 +1,4 @@
-"""Post-processors on the hot path: ``Deltas``, ``Standardize`` / ``CMVN``, ``Cepstra`` and ``SlidingCMVN``.
+"""Post-processors on the hot path: ``Deltas``, ``Standardize`` / ``CMVN``, ``Cepstra``, ``SlidingCMVN``, ``EnergyVAD``.
 
 Same classes, aliases, arguments and error behaviour as the reference's (post.py:38-491);
 the element-wise and stencil arithmetic runs in HIP kernels (``csrc/post.hip``) -- there
@@ -10,6 +10,10 @@ coefficients (MFCCs), one HIP kernel over the rows with the matrix built on the 
 
 ``SlidingCMVN`` is not in the reference either: mean (and variance) normalisation over a sliding window of frames,
 Kaldi's ``apply-cmvn-sliding``, one HIP kernel of the stages library (``csrc/sliding.hip``) over a packed ragged batch.
+
+``EnergyVAD`` is not in the reference either: Kaldi's energy-based voiced-frame decision (``compute-vad-energy``) and
+the selection of the voiced rows (``select-voiced-frames``), two HIP kernels of the stages library (``csrc/vad.hip``)
+over a packed ragged batch.
 
 ``Stack`` moves data only: views for a single tensor, one copy
 kernel for a packed ragged batch.  CMVN statistics files (``rfilename``, ``save``) go through
@@ -24,7 +28,7 @@ import numpy as np
 from . import _native
 from .alias import AliasedFactory
 
-__all__ = ["CMVN", "Cepstra", "Deltas", "PostProcessor", "SlidingCMVN", "Stack", "Standardize"]
+__all__ = ["CMVN", "Cepstra", "Deltas", "EnergyVAD", "PostProcessor", "SlidingCMVN", "Stack", "Standardize"]
 
 
 class PostProcessor(AliasedFactory):
@@ -942,3 +946,232 @@ class SlidingCMVN(PostProcessor):
             features[...] = res
             return features
         return res
+
+
+# ------------------------------------------------------------------ EnergyVAD --------
+
+_SELECT_TILE = 256  # rows of a block of pds_select_rows_w32 (include/pds_amd_stages.h)
+_SELECT_MAX_BLOCKS = (1 << 31) - 1  # ... and the blocks one call of it may launch
+
+
+def _vad_number(value, what):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"EnergyVAD: {what} must be a number, got {value!r}")
+    value = float(value)
+    if not np.isfinite(value):
+        raise ValueError(f"EnergyVAD: {what} must be finite, got {value!r}")
+    return value
+
+
+def _vad_index(value, what):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 0:
+        raise ValueError(f"EnergyVAD: {what} must be an integer that is not negative, got {value!r}")
+    if value >= 1 << 31:
+        raise ValueError(f"EnergyVAD: {what} must be below 2**31, got {value!r}")
+    return int(value)
+
+
+class EnergyVAD(PostProcessor):
+    """Energy-based voice activity detection: Kaldi's ``compute-vad-energy`` and ``select-voiced-frames``
+
+    `axis` of :func:`decide` / :func:`apply` is the *coefficient* axis; time is the axis in front of it (rows of a
+    ``(frames, coeffs)`` matrix).  Column `energy_col` of a row is the frame's log energy: column 0 of a computer built
+    with ``include_energy=True`` and of ``Cepstra(energy=True)``.  The defaults and the rule are Kaldi's
+    ``ComputeVadEnergy``.  For an utterance of ``T >= 1`` frames with energies ``e_t``, each widened to float64 first,
+
+        if energy_mean_scale != 0:
+            p_j = sum of e_t over t = j, j + 64, j + 128, .. in that order, starting from +0.0       (0 <= j < 64)
+            s   = +0.0;  for j = 0 .. 63 in order:  s += p_j
+            thr = energy_threshold + (energy_mean_scale * s) / T        (each operation rounded once, in float64)
+        else:
+            thr = energy_threshold                                       (the energies are not summed)
+        for frame t:  lo = max(0, t - frames_context);  hi = min(T - 1, t + frames_context)
+            den = hi - lo + 1;  num = the number of u in [lo, hi] with e_u > thr
+            voiced_t = float(num) >= float(den) * proportion_threshold
+
+    The 64 interleaved partial sums are part of the result, in its last bits: a wave of the device sums an utterance
+    with one partial per lane, and the host can reproduce the sum.  A NaN energy is never above the threshold; a NaN or
+    infinite sum makes every comparison false or true as IEEE says.  An utterance without frames gives no decisions.
+
+    Selection keeps the voiced rows, in order and byte for byte; an utterance without a voiced frame gives 0 rows
+    (Kaldi skips such an utterance).  float32 stays float32 and float64 stays float64; anything else is widened to
+    float64 first.
+
+    `select_last` is read by ``signals-to-torch-feat-dir`` only: the decisions are taken where the stage stands in
+    ``--postprocess``, the later stages see all frames, and the rows are dropped after the last stage -- Kaldi's order
+    (``compute-vad-energy``, ``apply-cmvn-sliding``, ``select-voiced-frames``).
+    """
+
+    aliases = {"vad", "energy_vad", "vad_energy"}
+
+    def __init__(self, energy_threshold: float = 5.0, energy_mean_scale: float = 0.5, frames_context: int = 0,
+                 proportion_threshold: float = 0.6, energy_col: int = 0, select_last: bool = False):
+        self.energy_threshold = _vad_number(energy_threshold, "energy_threshold")
+        self.energy_mean_scale = _vad_number(energy_mean_scale, "energy_mean_scale")
+        if self.energy_mean_scale < 0:
+            raise ValueError(f"EnergyVAD: energy_mean_scale must not be negative, got {energy_mean_scale!r}")
+        self.frames_context = _vad_index(frames_context, "frames_context")
+        self.proportion_threshold = _vad_number(proportion_threshold, "proportion_threshold")
+        if not 0.0 < self.proportion_threshold < 1.0:
+            raise ValueError(
+                f"EnergyVAD: proportion_threshold must lie strictly between 0 and 1, got {proportion_threshold!r}")
+        self.energy_col = _vad_index(energy_col, "energy_col")
+        if not isinstance(select_last, (bool, np.bool_)):
+            raise ValueError(f"EnergyVAD: select_last must be a bool, got {select_last!r}")
+        self.select_last = bool(select_last)
+
+    # -- packed ragged batches ----------------------------------------------------------------
+
+    @staticmethod
+    def _check_rows(feats, row_offsets):
+        torch = _native.require_device()
+        if not _is_gpu_tensor(feats) or feats.dtype not in (torch.float32, torch.float64) or feats.dim() != 2:
+            raise ValueError("feats must be a 2-D float32 or float64 GPU tensor")
+        R = feats.shape[0]
+        rows = np.ascontiguousarray(row_offsets, dtype=np.int64)
+        if rows.ndim != 1 or len(rows) < 1 or (np.diff(rows) < 0).any() or rows[0] < 0 or rows[-1] > R:
+            raise ValueError("row_offsets must be B + 1 ascending row indices within feats")
+        return torch, rows
+
+    def decide_rows(self, feats, row_offsets):
+        """The decisions of every utterance of a packed ragged batch, in one launch on the GPU
+
+        `feats`: ``(total_rows, C)`` float32 or float64 GPU tensor (rows may be strided: a column slice of a wider
+        tensor), utterance b in rows ``row_offsets[b]:row_offsets[b+1]``; empty utterances are allowed.  Returns
+        ``(voiced, counts)``: a uint8 GPU tensor ``(total_rows,)`` of 0 and 1 (0 in rows of no utterance), and the
+        host int64 ``(B,)`` numbers of voiced rows per utterance -- fetching them is the call's one synchronisation.
+        """
+        torch, rows = self._check_rows(feats, row_offsets)
+        lib = _native.stages_lib()
+        R, C = feats.shape
+        if self.energy_col >= C:
+            raise ValueError(f"EnergyVAD: energy_col = {self.energy_col}, but the rows have {C} coefficients")
+        B = len(rows) - 1
+        voiced = torch.zeros((R,), dtype=torch.uint8, device=feats.device)
+        if B <= 0 or R == 0:
+            return voiced, np.zeros(max(B, 0), dtype=np.int64)
+        meta, nrows = _rows_meta(rows, feats.device)
+        if not int(nrows.max()):
+            return voiced, np.zeros(B, dtype=np.int64)
+        col = feats[:, self.energy_col]
+        stride = col.stride(0) if R > 1 else 1
+        if stride < 1:
+            col, stride = col.contiguous(), 1
+        counts = torch.zeros((B,), dtype=torch.int64, device=feats.device)
+        fn = lib.pds_vad_energy_rows_f32 if feats.dtype == torch.float32 else lib.pds_vad_energy_rows_f64
+        with torch.cuda.device(feats.device):
+            # (one wave per utterance: B < 2**31 utterances are always one grid)
+            rc = fn(col.data_ptr(), stride, meta[0].data_ptr(), meta[1].data_ptr(), B, int(nrows.max()),
+                    self.energy_threshold, self.energy_mean_scale, self.frames_context, self.proportion_threshold,
+                    voiced.data_ptr(), counts.data_ptr(), _stream(torch, feats))
+            _native.check_stages(rc, "pds_vad_energy_rows")
+        return voiced, counts.cpu().numpy()
+
+    def _select(self, torch, feats, rows, keep, counts):
+        """the kept rows of `feats` (``keep``: uint8 GPU ``(R,)``; ``counts``: host kept rows per utterance)"""
+        lib = _native.stages_lib()
+        if feats.shape[1] and feats.stride(1) != 1:
+            feats = feats.contiguous()
+        R, C = feats.shape
+        new_offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        out = torch.empty((int(new_offsets[-1]), C), dtype=feats.dtype, device=feats.device)
+        B = len(rows) - 1
+        if B <= 0 or out.shape[0] == 0 or C == 0:
+            return out, new_offsets
+        meta, nrows = _rows_meta(rows, feats.device)
+        per = feats.element_size() // 4  # 32-bit words of an element
+        in_stride = (feats.stride(0) if R > 1 else C) * per
+        if in_stride < C * per:
+            raise ValueError("rows of feats must not overlap")
+        out_off = torch.from_numpy(new_offsets[:-1].copy()).to(feats.device)
+        # one launch, unless the batch needs more blocks (utterances x tiles of rows) than a grid has
+        tiles = -(-int(nrows.max()) // _SELECT_TILE)
+        step = max(1, min(B, _SELECT_MAX_BLOCKS // tiles))
+        with torch.cuda.device(feats.device):
+            for lo in range(0, B, step):
+                hi = min(B, lo + step)
+                rc = lib.pds_select_rows_w32(
+                    feats.data_ptr(), in_stride, C * per, meta[0, lo:].data_ptr(), meta[1, lo:].data_ptr(), hi - lo,
+                    int(nrows[lo:hi].max()), keep.data_ptr(), out_off[lo:].data_ptr(), out.data_ptr(), C * per,
+                    _stream(torch, feats))
+                _native.check_stages(rc, "pds_select_rows")
+        return out, new_offsets
+
+    def select_rows(self, feats, row_offsets, voiced):
+        """The rows of a packed ragged batch whose `voiced` is set, in order and byte for byte, in one launch
+
+        `feats`, `row_offsets` as for :func:`decide_rows`; `voiced`: a uint8 or bool mask of ``total_rows`` entries
+        (a GPU tensor, or an array that is uploaded).  Returns ``(out, out_row_offsets)``: the kept rows packed, and the
+        host int64 ``(B + 1,)`` offsets of the utterances in them, derived from the mask.
+        """
+        torch, rows = self._check_rows(feats, row_offsets)
+        R = feats.shape[0]
+        if not _is_gpu_tensor(voiced):
+            voiced = torch.from_numpy(np.ascontiguousarray(voiced)).to(feats.device)
+        if voiced.dtype not in (torch.uint8, torch.bool) or tuple(voiced.shape) != (R,) or voiced.device != feats.device:
+            raise ValueError("voiced must be a uint8 or bool mask with one entry per row of feats, on feats' device")
+        keep = voiced.contiguous()
+        keep = keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+        B = len(rows) - 1
+        if B <= 0 or R == 0:
+            counts = np.zeros(max(B, 0), dtype=np.int64)
+        else:
+            # kept rows in front of every row, gathered at the utterances' ends (32-bit while the rows allow it)
+            wide = torch.int32 if R < (1 << 31) else torch.int64
+            before = torch.zeros((R + 1,), dtype=wide, device=feats.device)
+            torch.cumsum(keep != 0, 0, dtype=wide, out=before[1:])
+            at = before[torch.from_numpy(rows).to(feats.device)]
+            counts = (at[1:] - at[:-1]).cpu().numpy().astype(np.int64)
+        return self._select(torch, feats, rows, keep, counts)
+
+    def apply_rows(self, feats, row_offsets):
+        """:func:`select_rows` of :func:`decide_rows`: the voiced rows of every utterance of a packed ragged batch.
+        Returns ``(out, out_row_offsets)``"""
+        voiced, counts = self.decide_rows(feats, row_offsets)
+        torch, rows = self._check_rows(feats, row_offsets)
+        return self._select(torch, feats, rows, voiced, counts)
+
+    # -- single tensors and arrays ------------------------------------------------------------
+
+    @staticmethod
+    def _device_rows(features, axis, dims, what):
+        """(on_gpu, float32 / float64 GPU tensor with the coefficients last)"""
+        on_gpu = _is_gpu_tensor(features)
+        if not on_gpu:
+            features = np.asarray(features)
+        if len(features.shape) not in dims:
+            raise ValueError(what)
+        torch = _native.require_device()
+        if on_gpu:
+            t = features if features.dtype in (torch.float32, torch.float64) else features.to(torch.float64)
+        else:
+            t = _to_device(features if features.dtype in (np.float32, np.float64) else features.astype(np.float64))
+        return on_gpu, t.movedim(axis % t.dim(), -1)
+
+    def decide(self, features, axis: int = -1):
+        """Which frames are voiced: a bool array (a bool GPU tensor for a GPU tensor) shaped like `features` without
+        its coefficient axis.  ``(frames, coeffs)``, or ``(batch, frames, coeffs)`` with every utterance decided by
+        itself"""
+        on_gpu, moved = self._device_rows(features, axis, (2, 3),
+                                          "EnergyVAD: expected (frames, coeffs) or (batch, frames, coeffs)")
+        lead = tuple(moved.shape)
+        T, C = lead[-2], lead[-1]
+        B = lead[0] if len(lead) == 3 else 1
+        rows = moved if moved.dim() == 2 else moved.reshape(B * T, C)
+        voiced, _ = self.decide_rows(rows, np.arange(B + 1, dtype=np.int64) * T)
+        voiced = voiced.view(_native.require_device().bool).reshape(lead[:-1])
+        return voiced if on_gpu else voiced.cpu().numpy()
+
+    def apply(self, features, axis: int = -1, in_place: bool = False):
+        """The voiced rows of one utterance, a 2-D array or tensor, in order.  A batch would come out ragged (use
+        :func:`apply_rows`) and the shape changes: 3-D input and ``in_place=True`` are ``ValueError`` s"""
+        if in_place:
+            raise ValueError("EnergyVAD: the number of rows changes, so there is no in_place")
+        nd = features.dim() if _is_gpu_tensor(features) else np.ndim(features)
+        if nd != 2:
+            raise ValueError("EnergyVAD: apply takes one utterance, (frames, coeffs): the voiced rows of a batch are "
+                             "ragged (apply_rows takes a packed batch)")
+        on_gpu, moved = self._device_rows(features, axis, (2,), "EnergyVAD: expected (frames, coeffs)")
+        out, _ = self.apply_rows(moved, np.asarray([0, moved.shape[0]], dtype=np.int64))
+        out = out.movedim(-1, axis % 2)
+        return out if on_gpu else out.cpu().numpy()
