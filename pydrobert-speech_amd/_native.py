@@ -1,5 +1,6 @@
-"""ctypes binding of ``libpds_amd.so`` (C ABI: ``include/pds_amd.h``) and of ``libpds_amd_stages.so``, the stage
-kernels outside the fused kernel's instantiation matrix (C ABI: ``include/pds_amd_stages.h``).
+"""ctypes binding of ``libpds_amd.so`` (C ABI: ``include/pds_amd.h``), of ``libpds_amd_stages.so``, the stage
+kernels outside the fused kernel's instantiation matrix (C ABI: ``include/pds_amd_stages.h``), and of
+``libpds_amd_stages2.so``, the second capped library of stage kernels (C ABI: ``include/pds_amd_stages2.h``).
 
 There is deliberately no fallback: if the shared library is missing or a compute call
 is made without a HIP device, an exception is raised.  Nothing in this package computes
@@ -14,6 +15,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PDS_AMD_LIB") or os.path.join(_HERE, "csrc", "libpds_amd.so")
 # ... and PDS_AMD_STAGES_LIB another build of the stages library
 STAGES_LIB_PATH = os.environ.get("PDS_AMD_STAGES_LIB") or os.path.join(_HERE, "csrc", "libpds_amd_stages.so")
+# ... and PDS_AMD_STAGES2_LIB another build of the second stages library; without it the file beside the first library
+STAGES2_LIB_PATH = os.environ.get("PDS_AMD_STAGES2_LIB") or os.path.join(os.path.dirname(LIB_PATH),
+                                                                         "libpds_amd_stages2.so")
 
 PDS_OK = 0
 
@@ -275,8 +279,36 @@ STAGES_SIGNATURES = {
     "pds_select_rows_w32": (c_int32, _SELECT_ROWS_ARGS),
 }
 
+_PCEN_SMOOTH_ARGS = [
+    c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32,  # d_in, in_stride, d_row_off, d_nrows, B, C
+    c_double, c_double, c_void_p, c_int64, c_void_p,  # smooth, oms, d_m, m_stride, stream
+]
+_PCEN_COMPRESS_ARGS = [
+    c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32,  # d_in, in_stride, d_m, m_stride, rows, C
+    c_double, c_double, c_double, c_double, c_double,  # gain, bias, power, eps, bp
+    c_void_p, c_int64, c_void_p,  # d_out, out_stride, stream
+]
+_MS_PCEN_ARGS = [
+    c_void_p, c_void_p, c_int64, c_int32,  # d_statics, d_state, capacity, C
+    c_double, c_double, c_double, c_double, c_double, c_double, c_double,  # smooth, oms, gain, bias, power, eps, bp
+    c_void_p, c_void_p, c_void_p, c_int32, c_void_p,  # d_ids, d_rows, d_fresh, n, stream
+]
+
+# name -> (restype, argtypes); every symbol include/pds_amd_stages2.h declares
+STAGES2_SIGNATURES = {
+    "pds_stages2_version": (c_int32, []),
+    "pds_stages2_last_error": (c_char_p, []),
+    "pds_pcen_smooth_rows_f32": (c_int32, _PCEN_SMOOTH_ARGS),
+    "pds_pcen_smooth_rows_f64": (c_int32, _PCEN_SMOOTH_ARGS),
+    "pds_pcen_compress_rows_f32": (c_int32, _PCEN_COMPRESS_ARGS),
+    "pds_pcen_compress_rows_f64": (c_int32, _PCEN_COMPRESS_ARGS),
+    "pds_multistream_pcen_f32": (c_int32, _MS_PCEN_ARGS),
+    "pds_multistream_pcen_f64": (c_int32, _MS_PCEN_ARGS),
+}
+
 _lib = None
 _stages_lib = None
+_stages2_lib = None
 
 
 def lib() -> ctypes.CDLL:
@@ -326,6 +358,28 @@ def stages_lib() -> ctypes.CDLL:
     return _stages_lib
 
 
+def stages2_lib() -> ctypes.CDLL:
+    """The loaded second stages library; raises :class:`NativeError` if it has not been built"""
+    global _stages2_lib
+    if _stages2_lib is None:
+        if not os.path.exists(STAGES2_LIB_PATH):
+            raise NativeError(
+                f"{STAGES2_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
+                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
+            )
+        try:  # (torch's HIP runtime first, as for lib())
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        loaded = ctypes.CDLL(STAGES2_LIB_PATH)
+        for name, (restype, argtypes) in STAGES2_SIGNATURES.items():
+            fn = getattr(loaded, name)  # AttributeError if the .so is stale
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _stages2_lib = loaded
+    return _stages2_lib
+
+
 def last_error() -> str:
     return lib().pds_last_error().decode("utf-8", "replace")
 
@@ -344,6 +398,15 @@ def check_stages(rc: int, what: str) -> None:
     """:func:`check` for a call into the stages library, which keeps its own error string"""
     if rc != PDS_OK:
         msg = stages_lib().pds_stages_last_error().decode("utf-8", "replace")
+        if rc == -1:
+            raise ValueError(f"{what}: {msg}")
+        raise NativeError(f"{what}: {msg} (code {rc})")
+
+
+def check_stages2(rc: int, what: str) -> None:
+    """:func:`check` for a call into the second stages library, which keeps its own error string"""
+    if rc != PDS_OK:
+        msg = stages2_lib().pds_stages2_last_error().decode("utf-8", "replace")
         if rc == -1:
             raise ValueError(f"{what}: {msg}")
         raise NativeError(f"{what}: {msg} (code {rc})")

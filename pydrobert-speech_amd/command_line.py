@@ -20,7 +20,9 @@ Same command line and on-disk result as the reference's tool -- a text map of
   post-processor over the packed rows (a ``Cepstra`` -- ``--postprocess '[{"name": "mfcc", "num_ceps": 13}]'`` --
   works row by row, so the whole batch is one call and one launch, and the row offsets stay as they are; a
   ``SlidingCMVN`` -- ``{"name": "sliding_cmvn", "cmn_window": 600}`` -- normalises every utterance by itself in one
-  launch over the packed rows, ``SlidingCMVN.apply_rows``; an ``EnergyVAD`` -- ``{"name": "vad"}`` -- decides and
+  launch over the packed rows, ``SlidingCMVN.apply_rows``; a ``PCEN`` -- ``{"name": "pcen", "smooth": 0.025}``, behind
+  a computer with ``"use_log": false`` -- normalises every utterance by itself over the packed rows where they stand,
+  ``PCEN.apply_rows``, and a computer that takes logs is a ``ValueError``; an ``EnergyVAD`` -- ``{"name": "vad"}`` -- decides and
   drops the unvoiced rows of every utterance on the device, ``EnergyVAD.apply_rows``, and the stages behind it see
   the shorter utterances; with ``"select_last": true`` it decides where it stands, the later stages see all frames
   and the rows are dropped after the last stage -- Kaldi's order, ``[{"name": "mfcc", "energy": true}, {"name":
@@ -46,7 +48,7 @@ import numpy as np
 
 from .alias import alias_factory_subclass_from_arg
 from .compute import FrameComputer
-from .post import Cepstra, Deltas, EnergyVAD, PostProcessor, SlidingCMVN, Stack, Standardize
+from .post import PCEN, Cepstra, Deltas, EnergyVAD, PostProcessor, SlidingCMVN, Stack, Standardize, refuse_log_computer
 from .pre import Dither, Preemphasize, PreProcessor, Resample
 from .util import SIGNAL_SOURCES, read_signal
 
@@ -121,6 +123,8 @@ class FeatureDirWriter:
         for pre in preprocessors:
             if not isinstance(pre, (Dither, Preemphasize, Resample)):
                 raise NotImplementedError(f"pre-processor {type(pre).__name__}")
+        if computer is not None and any(isinstance(post, PCEN) for post in postprocessors):
+            refuse_log_computer(computer)  # (PCEN takes linear energies)
         self.computer, self.pre, self.post = computer, list(preprocessors), list(postprocessors)
         self.out_dir, self.channel, self.force_as, self.seed = out_dir, channel, force_as, seed
         self.prefix, self.suffix, self.manifest = file_prefix, file_suffix, manifest
@@ -304,6 +308,8 @@ class FeatureDirWriter:
             return post.apply(feats, axis=-1), rows  # row by row: the whole packed batch in one launch, same rows
         elif isinstance(post, SlidingCMVN) and feats.dtype in (torch.float32, torch.float64):
             return post.apply_rows(feats, rows), rows  # every utterance by itself, the packed batch in one launch
+        elif isinstance(post, PCEN) and feats.dtype in (torch.float32, torch.float64):
+            return post.apply_rows(feats, rows), rows  # every utterance's smoother by itself, the packed batch at once
         elif isinstance(post, Standardize) and post.have_stats:
             return post.apply(feats, axis=-1), rows  # one global transform: the whole batch at once
         elif isinstance(post, Standardize) and feats.dtype == torch.float32 and feats.shape[0]:

@@ -17,6 +17,7 @@ samples of up to `capacity` streams in a device pool and takes every stream that
     sb = StreamBatch(computer, capacity=4096, dither=Dither(1.0, seed=5))   # Dither over every stream's whole signal
     sb = StreamBatch(computer, capacity=4096, cepstra=Cepstra(13))  # cepstral coefficients of every row, see below
     sb = StreamBatch(computer, capacity=4096, sliding_cmvn=SlidingCMVN(600, 1))  # sliding-window CMVN, see below
+    sb = StreamBatch(computer, capacity=4096, pcen=PCEN())         # per-channel energy normalisation, see below
 
 Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
 the same chunks: the same row counts, dtype and -- for float32 and float64 samples -- the same values bit for bit as
@@ -39,7 +40,7 @@ the assemble launch (``compute_chunks`` only), the feature launch, the commit or
 post stages.  A class adds what differs through four hooks: its host state, the order in which the emitting streams
 launch, its extra rows of launch metadata, and the feature launch itself.
 
-The post stages -- cepstra, cmvn or sliding-window cmvn, deltas, stack, in that order -- are objects of one protocol,
+The post stages -- pcen, cepstra, cmvn or sliding-window cmvn, deltas, stack, in that order -- are objects of one protocol,
 :class:`_Stage`, which the constructor lists and the tick loops over twice.  A stage owns its parsed spec, its host
 state (``DeltaState`` ...; none for cepstra), its device pools, its typed entry point -- looked up when the stage is
 built, so a library without it is an ``AttributeError`` for the batch that asks for the stage and no other -- and the
@@ -125,6 +126,19 @@ in float64, and one launch per tick (``pds_multistream_sliding_*`` of the stages
 every stream's new rows in order, in place.  ``finalize`` normalises the last rows like any others and returns the
 stream to fresh.
 
+With `pcen` (a :class:`post.PCEN`, over a computer that does not take logs) every static row is normalised per column
+by the stream's one-pole smoother and root-compressed -- the first post stage of a tick, before `cepstra`, `cmvn` /
+`sliding_cmvn`, `deltas` and `stack`, which see its rows; widths and the look-ahead do not change.  A stream's rows are
+those of the offline chain ``stack(deltas(cmvn(cepstra(pcen.apply(statics)))))`` over its whole utterance, bit for bit,
+whatever the cuts: the smoother is a recurrence of one float64 per column, which a pool of ``capacity * F`` float64
+keeps across ticks exactly, and the compression is the one function the offline kernels inline
+(``csrc/pcen_rule.h``).  :class:`PcenState` knows per stream whether it is fresh -- its next row is the first of its
+utterance, where ``M = E``; one launch per tick that has rows (``pds_multistream_pcen_*`` of the second stages library,
+``csrc/pcen.hip``) takes every stream's new rows in order, in place, smoother and compression fused: a tick has one to
+a few rows per stream.  The upload grows by the fresh flags, one byte per stream, and by what tells the kernel where a
+stream's rows lie: its id and its first row, a word each (no section of a ``finalize`` tick carries them).
+``finalize`` returns a stream to fresh.  :func:`StreamBatch.pcen_smooth` reads the streams' current M.
+
 With `stack` (a :class:`post.Stack`: frames along the row axis, ``pad_mode`` None, "edge" or "constant") every
 ``nv = num_vectors`` consecutive rows of a stream become one row of ``nv`` times the width -- the last stage, after
 `cmvn` and `deltas`: a stream's rows, concatenated over its ``compute_chunks`` calls and its ``finalize``, are
@@ -150,12 +164,12 @@ import numpy as np
 from . import _native, config
 from .alias import alias_factory_subclass_from_arg
 from .compute import PackedLayout, ShortTimeFourierTransformFrameComputer
-from .post import Cepstra, Deltas, PostProcessor, SlidingCMVN, Stack, Standardize
+from .post import PCEN, Cepstra, Deltas, PostProcessor, SlidingCMVN, Stack, Standardize, refuse_log_computer
 from .pre import Dither, Preemphasize, PreProcessor, dither_keys
 
-__all__ = ["CmvnState", "DeltaState", "DitherState", "SlidingState", "StackState", "StreamBatch", "StreamState",
-           "streaming_cepstra", "streaming_cmvn", "streaming_deltas", "streaming_dither", "streaming_preemphasis",
-           "streaming_sliding_cmvn", "streaming_stack"]
+__all__ = ["CmvnState", "DeltaState", "DitherState", "PcenState", "SlidingState", "StackState", "StreamBatch",
+           "StreamState", "streaming_cepstra", "streaming_cmvn", "streaming_deltas", "streaming_dither", "streaming_pcen",
+           "streaming_preemphasis", "streaming_sliding_cmvn", "streaming_stack"]
 
 _FIELDS = 8  # int64 per entry of pds_multistream_assemble's metadata (include/pds_amd.h)
 _DFIELDS = 8  # ... and of pds_multistream_deltas'
@@ -672,6 +686,65 @@ class SlidingState:
         meta[:, 5:] = 0
 
 
+def streaming_pcen(pcen, computer=None) -> Optional[PCEN]:
+    """`pcen` as :class:`StreamBatch` takes it -- a :class:`post.PCEN` or what
+    ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one (``"pcen"``, ``{"name": "pcen", "smooth": 0.025}``)
+    -> the ``PCEN``, or None for ``pcen=None``; ``ValueError`` for anything else and, given the `computer`, for one that
+    takes logs"""
+    if pcen is None:
+        return None
+    pcen = _post_processor("pcen", pcen, PCEN)
+    if computer is not None:
+        refuse_log_computer(computer)
+    return pcen
+
+
+class PcenState:
+    """Host bookkeeping of the PCEN smoother of many streams.  Needs no device.
+
+    Per stream: whether it is ``live`` -- it has had a static row since its start or last ``finalize``, so its slot of
+    the device pool holds its last M; a stream that is not is ``fresh``: its next row is the first of its utterance
+    (``M = E``), and its slot is not read.
+    """
+
+    def __init__(self, capacity: int):
+        capacity = int(capacity)
+        if capacity <= 0:
+            raise ValueError("capacity must be positive")
+        self.capacity = capacity
+        self.live = np.zeros(capacity, dtype=bool)
+
+    @property
+    def fresh(self) -> np.ndarray:
+        return ~self.live
+
+    def step(self, ids: np.ndarray, k: np.ndarray, final: bool = False) -> dict:
+        """What a tick that brings streams `ids` `k` new static frames does, without changing the state: per stream
+        whether it is `fresh` before the tick and whether it is live after it"""
+        k = np.asarray(k, dtype=np.int64)
+        live = self.live[ids]
+        return dict(k=k, fresh=~live, next_live=live | (k > 0), final=bool(final))
+
+    def commit(self, ids: np.ndarray, step: dict) -> None:
+        if step["final"]:
+            self.reset(ids)  # (the next utterance on the id starts its smoother anew)
+        else:
+            self.live[ids] = step["next_live"]
+
+    def reset(self, ids: np.ndarray) -> None:
+        self.live[ids] = False
+
+    def fill_meta(self, d_ids: np.ndarray, d_rows: np.ndarray, d_fresh: np.ndarray, ids: np.ndarray, step: dict,
+                  rows: np.ndarray) -> None:
+        """pds_multistream_pcen's three arrays of a tick: the stream ids into `d_ids` (int64[n]), every stream's first
+        row in the tick's statics and the end of the last one's, `rows`, into `d_rows` (int64[n + 1]), and the fresh
+        flags, one byte per stream, into the front of the words `d_fresh` (int64[ceil(n / 8)])"""
+        d_ids[:] = ids
+        d_rows[:] = rows
+        d_fresh[:] = 0
+        d_fresh.view(np.uint8)[: len(ids)] = step["fresh"]
+
+
 def streaming_stack(stack) -> Optional[Tuple[Stack, int, int, float]]:
     """`stack` as :class:`StreamBatch` takes it -- a :class:`post.Stack` or what
     ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one -> ``(Stack, num_vectors, pad, fill)`` with `pad`
@@ -828,15 +901,15 @@ def _place(sections):
 
 
 @functools.lru_cache(maxsize=256)  # (a batch's ticks repeat a few sizes: each is placed once)
-def _tick_layout(n, E, launch_rows, chunks, deltas, cmvn, stack=False, dither=False, sliding=False):
+def _tick_layout(n, E, launch_rows, chunks, deltas, cmvn, stack=False, dither=False, sliding=False, pcen=False):
     """The sections behind the samples in the upload of a tick over `n` streams of which `E` emit frames, placed: the
     assemble metadata and the tile prefix (`chunks`: a ``compute_chunks`` tick; ``finalize`` has neither, and no
     samples), the launch metadata -- `launch_rows` rows, one column per emitting stream --, the deltas metadata and
     the element prefix (`deltas`), the cmvn metadata (`cmvn`), the stack metadata and its element prefix (`stack`), the
     positions and keys of the dither (`dither`, in a ``compute_chunks`` tick), the sliding-window cmvn metadata
-    (`sliding`)"""
-    # (a batch without `stack` / `dither` / `sliding` has the layout it had before there was one: their sections are
-    # not placed at all)
+    (`sliding`), the ids, row prefix and fresh bytes of the PCEN (`pcen`)"""
+    # (a batch without `stack` / `dither` / `sliding` / `pcen` has the layout it had before there was one: their
+    # sections are not placed at all)
     return _place((("assemble", (n if chunks else 0, _FIELDS)),
                    ("tiles", (n + 1 if chunks else 0,)),
                    ("launch", (launch_rows, E)),
@@ -845,7 +918,8 @@ def _tick_layout(n, E, launch_rows, chunks, deltas, cmvn, stack=False, dither=Fa
                    ("cmvn", (n if cmvn else 0, _CFIELDS)))
                   + ((("stack", (n, _KFIELDS)), ("stack_elems", (n + 1,))) if stack else ())
                   + ((("dither", (n if chunks else 0, 2)),) if dither else ())
-                  + ((("sliding", (n, _WFIELDS)),) if sliding else ()))
+                  + ((("sliding", (n, _WFIELDS)),) if sliding else ())
+                  + ((("pcen_ids", (n,)), ("pcen_rows", (n + 1,)), ("pcen_fresh", ((n + 7) // 8,))) if pcen else ()))
 
 
 class _Stage:
@@ -894,6 +968,40 @@ class _Stage:
 
     def release(self):
         self.pools = {}
+
+
+class _PcenStage(_Stage):
+    """`pcen`, a kernel of the second stages library: the first post stage, in place.  Pool: ``smooth``, every
+    stream's last M, float64 ``(capacity, F)`` (a fresh stream's is not read: no fill)"""
+
+    sections = ("pcen_ids", "pcen_rows", "pcen_fresh")
+
+    def __init__(self, batch, spec, width):
+        super().__init__(batch, spec, width)
+        self.state = PcenState(batch.capacity)
+        self._fn = _typed(_native.stages2_lib(), "pds_multistream_pcen", batch.dtype)
+        self.pools["smooth"] = batch._torch.empty((batch.capacity, width), dtype=batch._torch.float64,
+                                                  device=batch.device)
+
+    def plan(self, up, ids, rows, final):
+        step = self._step = self.state.step(ids, rows[1:] - rows[:-1], final=final)
+        self.state.fill_meta(*map(up.host, self.sections), ids, step, rows)
+        return rows
+
+    def _run(self, statics, out, sections, n, step, stream):
+        spec = self.spec
+        rc = self._fn(statics.data_ptr(), self.pools["smooth"].data_ptr(), self.b.capacity, self.width, spec.smooth_coeff,
+                      spec.oms, spec.gain, spec.bias, spec.power, spec.eps, spec.bp, *sections, n, stream)
+        _native.check_stages2(rc, "pds_multistream_pcen")
+
+    def smooth(self, ids: np.ndarray) -> np.ndarray:
+        """:func:`StreamBatch.pcen_smooth` of the checked `ids`"""
+        out = np.full((len(ids), self.width), np.nan, dtype=np.float64)
+        live = np.flatnonzero(self.state.live[ids])
+        if len(live):
+            at = self.b._torch.from_numpy(ids[live]).to(self.b.device)
+            out[live] = self.pools["smooth"][at].cpu().numpy()
+        return out
 
 
 class _CepstraStage(_Stage):
@@ -1031,13 +1139,14 @@ class _TickBatch:
     :func:`_emit_order` (which order the emitting streams launch in), `_launch_extra` (the keys of a step that follow
     offset, length, frame count and first row in the launch metadata, a row each) and :func:`_feature_launch`.  The
     post stages are `_stages`, :class:`_Stage` objects by name, built by the constructor in the order they run;
-    `_tick` and `close` loop over it, and `dstate`, `cstate`, `wstate` and `kstate` are the states of its members."""
+    `_tick` and `close` loop over it, and `dstate`, `cstate`, `wstate`, `kstate` and `estate` are the states of its
+    members."""
 
     _computer_type = _wrong_computer = None
     _launch_extra = ()
 
     def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None, cmvn=None,
-                 cmvn_running=True, stack=None, dither=None, cepstra=None, sliding_cmvn=None):
+                 cmvn_running=True, stack=None, dither=None, cepstra=None, sliding_cmvn=None, pcen=None):
         # every argument is read before a device is touched
         if not isinstance(computer, self._computer_type):
             raise TypeError(self._wrong_computer)
@@ -1045,6 +1154,7 @@ class _TickBatch:
         if dtype not in (np.float32, np.float64):
             raise TypeError("StreamBatch: samples must be float32 or float64")
         dspec, coeff = streaming_deltas(deltas), streaming_preemphasis(preemphasis)
+        espec = streaming_pcen(pcen, computer)
         # the width the cmvn sees is the cepstral one with `cepstra` (whose bounds on the computer's width are checked
         # here, where it is known)
         pspec = streaming_cepstra(cepstra)
@@ -1099,7 +1209,8 @@ class _TickBatch:
         width = self._F0
         if cspec is not None:
             cspec += (bool(cmvn_running),)
-        for name, kind, spec in (("cepstra", _CepstraStage, pspec), ("cmvn", _CmvnStage, cspec),
+        for name, kind, spec in (("pcen", _PcenStage, espec), ("cepstra", _CepstraStage, pspec),
+                                 ("cmvn", _CmvnStage, cspec),
                                  ("sliding", _SlidingStage, wspec), ("deltas", _DeltasStage, dspec),
                                  ("stack", _StackStage, kspec)):
             if spec is not None:
@@ -1112,6 +1223,9 @@ class _TickBatch:
         # what a tick asks of _tick_layout: a stage's sections are placed if it is there
         self._layout_flags = (*(flag in states for flag in ("deltas", "cmvn", "stack")), self.nstate is not None,
                               "sliding" in states)
+        self.estate = states.get("pcen")
+        if self.estate is not None:  # (a batch without the stage asks for the layout as it did before there was one)
+            self._layout_flags += (True,)
 
     # ---- public interface -----------------------------------------------------------
 
@@ -1154,6 +1268,15 @@ class _TickBatch:
         if self.cstate is None:
             raise ValueError(f"{type(self).__name__} was built without cmvn")
         return self._stages["cmvn"].stats(self.state.check_ids(ids))
+
+    def pcen_smooth(self, ids) -> np.ndarray:
+        """the current smoother output M of streams `ids` (with `pcen`): host float64 ``[len(ids), F]``, the M of each
+        stream's last static row; NaN rows for a stream that is fresh (at its start or after its ``finalize``).  Reads
+        the device (one synchronisation) unless every stream is fresh"""
+        self._check_open()
+        if self.estate is None:
+            raise ValueError(f"{type(self).__name__} was built without pcen")
+        return self._stages["pcen"].smooth(self.state.check_ids(ids))
 
     def compute_chunks(self, ids, chunks: Sequence) -> List[np.ndarray]:
         """``compute_chunk`` of ``chunks[i]`` (1-D host array) for stream ``ids[i]``; returns the list of feature
@@ -1457,6 +1580,15 @@ class StreamBatch(_TickBatch):
     float64 sums -- 96 KB per stream at ``cmn_window = 600``, ``F = 40`` and float32 (601 * 40 * 4 + 640 bytes), 394 MB
     at the default capacity of 4096: size `capacity` to the streams that are live.  A tick's upload grows by eight
     words per stream.
+
+    `pcen`: a :class:`post.PCEN` (or what ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one:
+    ``"pcen"``, ``{"name": "pcen", "smooth": 0.025}``); ``None``: none.  The first post stage, before `cepstra`: every
+    static row is normalised by the stream's per-column smoother and compressed, and a stream's rows are
+    ``stack(deltas(cmvn(cepstra(pcen.apply(statics, axis=0)))))`` of the offline objects over its whole utterance, bit
+    for bit.  PCEN takes linear energies: a computer built with ``use_log=True`` is a ``ValueError``.  Widths and
+    :attr:`lookahead` do not change; ``finalize`` returns a stream to fresh; :func:`pcen_smooth` reads a stream's
+    current M.  Additional device memory: ``capacity * F`` float64.  A tick's upload grows by two words and one byte
+    per stream.
 
     `dither`: a :class:`pre.Dither` (or what ``alias_factory_subclass_from_arg(PreProcessor, ...)`` makes one:
     ``"dither"``, ``{"name": "dither", "coeff": 1.0, "seed": 5}``); ``None`` or a coefficient of 0: none.  Every

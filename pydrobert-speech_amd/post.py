@@ -1,4 +1,5 @@
-"""Post-processors on the hot path: ``Deltas``, ``Standardize`` / ``CMVN``, ``Cepstra``, ``SlidingCMVN``, ``EnergyVAD``.
+"""Post-processors on the hot path: ``Deltas``, ``Standardize`` / ``CMVN``, ``Cepstra``, ``SlidingCMVN``, ``EnergyVAD``,
+``PCEN``.
 
 Same classes, aliases, arguments and error behaviour as the reference's (post.py:38-491);
 the element-wise and stencil arithmetic runs in HIP kernels (``csrc/post.hip``) -- there
@@ -15,6 +16,10 @@ Kaldi's ``apply-cmvn-sliding``, one HIP kernel of the stages library (``csrc/sli
 the selection of the voiced rows (``select-voiced-frames``), two HIP kernels of the stages library (``csrc/vad.hip``)
 over a packed ragged batch.
 
+``PCEN`` is not in the reference either: per-channel energy normalisation of linear filter-bank energies, a one-pole
+smoother per column and a root compression, two HIP kernels of the second stages library (``csrc/pcen.hip``) over a
+packed ragged batch.
+
 ``Stack`` moves data only: views for a single tensor, one copy
 kernel for a packed ragged batch.  CMVN statistics files (``rfilename``, ``save``) go through
 ``util.read_signal`` / numpy.
@@ -28,7 +33,7 @@ import numpy as np
 from . import _native
 from .alias import AliasedFactory
 
-__all__ = ["CMVN", "Cepstra", "Deltas", "EnergyVAD", "PostProcessor", "SlidingCMVN", "Stack", "Standardize"]
+__all__ = ["CMVN", "Cepstra", "Deltas", "EnergyVAD", "PCEN", "PostProcessor", "SlidingCMVN", "Stack", "Standardize"]
 
 
 class PostProcessor(AliasedFactory):
@@ -1175,3 +1180,220 @@ class EnergyVAD(PostProcessor):
         out, _ = self.apply_rows(moved, np.asarray([0, moved.shape[0]], dtype=np.int64))
         out = out.movedim(-1, axis % 2)
         return out if on_gpu else out.cpu().numpy()
+
+
+# ------------------------------------------------------------------ PCEN -------------
+
+
+def _pcen_number(value, what):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"PCEN: {what} must be a number, got {value!r}")
+    value = float(value)
+    if not np.isfinite(value):
+        raise ValueError(f"PCEN: {what} must be finite, got {value!r}")
+    return value
+
+
+def refuse_log_computer(computer) -> None:
+    """``ValueError`` if `computer` (an STFT or short-integration frame computer) takes the logarithm of its
+    energies (its ``use_log``): PCEN takes linear energies"""
+    if bool(getattr(computer, "_log", False)):
+        raise ValueError("PCEN takes linear energies: the computer takes their logarithm (build it with use_log=False)")
+
+
+class PCEN(PostProcessor):
+    """Per-channel energy normalisation (PCEN; Wang et al. 2017, ``librosa.pcen``): a one-pole automatic gain control
+    per column followed by a root compression, in place of ``log`` and utterance-level CMVN
+
+    `axis` of :func:`apply` / :func:`smooth` is the *time* axis; every other axis holds independent columns.
+
+    The definition.
+
+    Per utterance of T >= 1 rows and per column c, in float64, every operation rounded by itself (no contraction):
+
+    1. oms = 1.0 - smooth, rounded once on the host, and bp = bias ** power as numpy float64 on the host.  Both are
+       passed to the kernels as arguments.  The device never recomputes them.
+    2. M[0] = E[0], widened exactly.  For t >= 1, M[t] = (oms * M[t-1]) + (smooth * E[t]): two products and one sum,
+       each rounded once.  This is librosa's steady-state start.
+    3. y[t] = pow(E[t] / pow(eps + M[t], gain) + bias, power) - bp.  Every operation is float64.  There are no special
+       cases for particular exponents.  The result is rounded once to the row type.
+
+    The output has the input's type (float32 or float64) and shape.  Every column is treated alike, including an energy
+    column.  The input is meant to be the non-negative linear energies of a computer with use_log=False.  A negative
+    base gives what IEEE pow gives.  A NaN or infinite E[t] stays in M for the rest of the utterance, because a one-pole
+    filter does not forget.  T = 0 gives nothing.
+
+    M is plain IEEE arithmetic, which numpy reproduces bit for bit (:func:`smooth_rows` returns it).  y goes through the
+    device's ``pow``, which is not numpy's: it agrees with a numpy model within the float32 / float64 tolerances of this
+    package, and it is bit-identical between :func:`apply`, :func:`apply_rows` and ``StreamBatch(pcen=...)``, whatever
+    the cuts of a stream.  Anything but float32 and float64 input is widened to float64 first.
+
+    The object keeps `smooth` as ``smooth_coeff`` (:func:`smooth` is the method that returns M), ``oms`` and ``bp`` as
+    the kernels are given them, and the other arguments under their names.
+    """
+
+    aliases = {"pcen", "per_channel_energy_norm"}
+
+    def __init__(self, smooth: float = 0.025, gain: float = 0.98, bias: float = 2.0, power: float = 0.5,
+                 eps: float = 1e-6):
+        self.smooth_coeff = _pcen_number(smooth, "smooth")  # (`smooth` itself is the method that returns M)
+        self.gain = _pcen_number(gain, "gain")
+        self.bias = _pcen_number(bias, "bias")
+        self.power = _pcen_number(power, "power")
+        self.eps = _pcen_number(eps, "eps")
+        if not 0.0 < self.smooth_coeff <= 1.0:
+            raise ValueError(f"PCEN: smooth must lie in (0, 1], got {smooth!r}")
+        if self.gain < 0.0:
+            raise ValueError(f"PCEN: gain must not be negative, got {gain!r}")
+        if self.bias < 0.0:
+            raise ValueError(f"PCEN: bias must not be negative, got {bias!r}")
+        if not self.power > 0.0:
+            raise ValueError(f"PCEN: power must be positive, got {power!r}")
+        if not self.eps > 0.0:
+            raise ValueError(f"PCEN: eps must be positive, got {eps!r}")
+        # what the kernels are given and never recompute (step 1 of the definition)
+        self.oms = float(np.float64(1.0) - np.float64(self.smooth_coeff))
+        self.bp = float(np.float64(self.bias) ** np.float64(self.power))
+
+    @classmethod
+    def from_time_constant(cls, time_constant_s: float = 0.4, frame_shift_ms: float = 10.0, **kw):
+        """``PCEN(smooth=s, **kw)`` with librosa's rule for the smoother: ``T = time_constant_s / (frame_shift_ms /
+        1000)`` frames and ``s = (sqrt(1 + 4 T**2) - 1) / (2 T**2)``, computed in float64 on the host"""
+        if "smooth" in kw:
+            raise ValueError("PCEN.from_time_constant: the time constant gives smooth; do not pass it")
+        tc = _pcen_number(time_constant_s, "time_constant_s")
+        shift = _pcen_number(frame_shift_ms, "frame_shift_ms")
+        if not tc > 0.0 or not shift > 0.0:
+            raise ValueError("PCEN.from_time_constant: time_constant_s and frame_shift_ms must be positive")
+        T = np.float64(tc) / (np.float64(shift) / np.float64(1000.0))
+        smooth = (np.sqrt(np.float64(1.0) + np.float64(4.0) * T * T) - np.float64(1.0)) / (np.float64(2.0) * T * T)
+        return cls(smooth=float(smooth), **kw)
+
+    # ---- packed ragged batches ------------------------------------------------------
+
+    @staticmethod
+    def _check_rows(torch, feats, row_offsets):
+        if not _is_gpu_tensor(feats) or feats.dtype not in (torch.float32, torch.float64) or feats.dim() != 2:
+            raise ValueError("feats must be a 2-D float32 or float64 GPU tensor")
+        if feats.shape[1] and feats.stride(1) != 1:
+            feats = feats.contiguous()
+        R, C = feats.shape
+        rows = np.ascontiguousarray(row_offsets, dtype=np.int64)
+        if rows.ndim != 1 or len(rows) < 1 or (np.diff(rows) < 0).any() or rows[0] < 0 or rows[-1] > R:
+            raise ValueError("row_offsets must be B + 1 ascending row indices within feats")
+        stride = feats.stride(0) if R > 1 else C
+        if stride < C:
+            raise ValueError("rows of feats must not overlap")
+        return feats, rows, stride
+
+    def _smooth_into(self, torch, lib, feats, rows, stride, m):
+        """the smoother's launches over the checked batch: M of every utterance into float64 `m`, ``(R, C)``"""
+        R, C = feats.shape
+        B = len(rows) - 1
+        meta, _ = _rows_meta(rows, feats.device)
+        fn = lib.pds_pcen_smooth_rows_f32 if feats.dtype == torch.float32 else lib.pds_pcen_smooth_rows_f64
+        # one launch, unless the batch needs more lanes (utterances x C) than a grid has blocks for
+        step = max(1, min(B, ((1 << 31) - 1) * 256 // C))
+        with torch.cuda.device(feats.device):
+            for lo in range(0, B, step):
+                hi = min(B, lo + step)
+                rc = fn(feats.data_ptr(), stride, meta[0, lo:].data_ptr(), meta[1, lo:].data_ptr(), hi - lo, C,
+                        self.smooth_coeff, self.oms, m.data_ptr(), C, _stream(torch, feats))
+                _native.check_stages2(rc, "pds_pcen_smooth_rows")
+
+    def smooth_rows(self, feats, row_offsets):
+        """The smoother's output M of every utterance of a packed ragged batch (step 2 of the definition): a float64
+        GPU tensor shaped like `feats`.  `feats` and `row_offsets` as :func:`apply_rows` takes them; rows of `feats`
+        outside ``row_offsets[0]:row_offsets[-1]`` are not written"""
+        torch = _native.require_device()
+        lib = _native.stages2_lib()
+        feats, rows, stride = self._check_rows(torch, feats, row_offsets)
+        R, C = feats.shape
+        m = torch.empty((R, C), dtype=torch.float64, device=feats.device)
+        if len(rows) > 1 and R and C and rows[-1] > rows[0]:
+            self._smooth_into(torch, lib, feats, rows, stride, m)
+        return m
+
+    def apply_rows(self, feats, row_offsets, out=None):
+        """Every utterance of a packed ragged batch normalised by itself, in two launches on the GPU
+
+        `feats`: ``(total_rows, C)`` float32 or float64 GPU tensor (rows may be strided: a column slice of a wider
+        tensor), utterance b in rows ``row_offsets[b]:row_offsets[b+1]``; empty and one-row utterances are allowed.
+        Returns a tensor of the same shape and dtype (`out`, if given; it may be `feats` itself: the second launch is
+        elementwise).  Rows outside ``row_offsets[0]:row_offsets[-1]`` are not written.
+        """
+        torch = _native.require_device()
+        lib = _native.stages2_lib()
+        feats, rows, stride = self._check_rows(torch, feats, row_offsets)
+        R, C = feats.shape
+        if out is None:
+            out = torch.empty((R, C), dtype=feats.dtype, device=feats.device)
+        elif (not _is_gpu_tensor(out) or out.dtype != feats.dtype or out.device != feats.device
+              or tuple(out.shape) != (R, C) or (C and out.stride(1) != 1)):
+            raise ValueError("out must be a GPU tensor of feats' shape, dtype and device with contiguous rows")
+        out_stride = out.stride(0) if R > 1 else C
+        if out_stride < C:
+            raise ValueError("rows of out must not overlap")
+        first, last = int(rows[0]), int(rows[-1])
+        if len(rows) <= 1 or R == 0 or C == 0 or last == first:
+            return out
+        m = torch.empty((R, C), dtype=torch.float64, device=feats.device)
+        self._smooth_into(torch, lib, feats, rows, stride, m)
+        fn = lib.pds_pcen_compress_rows_f32 if feats.dtype == torch.float32 else lib.pds_pcen_compress_rows_f64
+        with torch.cuda.device(feats.device):
+            rc = fn(feats[first:].data_ptr(), stride, m[first:].data_ptr(), C, last - first, C, self.gain, self.bias,
+                    self.power, self.eps, self.bp, out[first:].data_ptr(), out_stride, _stream(torch, feats))
+            _native.check_stages2(rc, "pds_pcen_compress_rows")
+        return out
+
+    # ---- arrays and tensors ---------------------------------------------------------
+
+    @staticmethod
+    def _device_rows(features, axis):
+        """`features` on the device as ``(B * T, C)`` rows with time in front of the columns -> (on_gpu, features, rows,
+        B, T, the shape with time moved to -2)"""
+        on_gpu = _is_gpu_tensor(features)
+        if not on_gpu:
+            features = np.asarray(features)
+        shape = tuple(features.shape)
+        if len(shape) not in (2, 3):
+            raise ValueError("PCEN: expected a 2-D or 3-D array or tensor")
+        axis = axis % len(shape)
+        torch = _native.require_device()
+        if on_gpu:
+            t = features if features.dtype in (torch.float32, torch.float64) else features.to(torch.float64)
+        else:
+            t = _to_device(features if features.dtype in (np.float32, np.float64) else features.astype(np.float64))
+        # time in front of the last axis; what is in front of time are utterances, what is behind it columns
+        moved = t.movedim(axis, -2)
+        lead = tuple(moved.shape)
+        T, C = lead[-2], lead[-1]
+        B = lead[0] if len(lead) == 3 else 1
+        if moved.dim() == 2 and moved.stride(1) == 1 and (moved.stride(0) >= C or T <= 1):
+            rows = moved  # a matrix whose rows are contiguous goes as it is, whatever its row stride
+        else:
+            rows = moved.reshape(B * T, C).contiguous()
+        return on_gpu, features, rows, B, T, lead
+
+    def smooth(self, features, axis: int = -1):
+        """The smoother's output M (step 2 of the definition) as float64, shaped like `features`: a numpy array for an
+        array, a GPU tensor for a GPU tensor"""
+        on_gpu, _, rows, B, T, lead = self._device_rows(features, axis)
+        m = self.smooth_rows(rows, np.arange(B + 1, dtype=np.int64) * T)
+        m = m.reshape(lead).movedim(-2, axis % len(lead))
+        return m if on_gpu else m.cpu().numpy()
+
+    def apply(self, features, axis: int = -1, in_place: bool = False):
+        on_gpu, features, rows, B, T, lead = self._device_rows(features, axis)
+        out = self.apply_rows(rows, np.arange(B + 1, dtype=np.int64) * T)
+        out = out.reshape(lead).movedim(-2, axis % len(lead))
+        if on_gpu:
+            if in_place and features.dtype == out.dtype:
+                features.copy_(out)
+                return features
+            return out
+        res = out.cpu().numpy()
+        if in_place and features.dtype == res.dtype and features.flags.writeable:
+            features[...] = res
+            return features
+        return res
