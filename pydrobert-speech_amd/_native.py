@@ -1,6 +1,7 @@
 """ctypes binding of ``libpds_amd.so`` (C ABI: ``include/pds_amd.h``), of ``libpds_amd_stages.so``, the stage
-kernels outside the fused kernel's instantiation matrix (C ABI: ``include/pds_amd_stages.h``), and of
-``libpds_amd_stages2.so``, the second capped library of stage kernels (C ABI: ``include/pds_amd_stages2.h``).
+kernels outside the fused kernel's instantiation matrix (C ABI: ``include/pds_amd_stages.h``), of
+``libpds_amd_stages2.so``, the second capped library of stage kernels (C ABI: ``include/pds_amd_stages2.h``), and of
+``libpds_amd_stages3.so``, the third (C ABI: ``include/pds_amd_stages3.h``).
 
 There is deliberately no fallback: if the shared library is missing or a compute call
 is made without a HIP device, an exception is raised.  Nothing in this package computes
@@ -18,6 +19,9 @@ STAGES_LIB_PATH = os.environ.get("PDS_AMD_STAGES_LIB") or os.path.join(_HERE, "c
 # ... and PDS_AMD_STAGES2_LIB another build of the second stages library; without it the file beside the first library
 STAGES2_LIB_PATH = os.environ.get("PDS_AMD_STAGES2_LIB") or os.path.join(os.path.dirname(LIB_PATH),
                                                                          "libpds_amd_stages2.so")
+# ... and PDS_AMD_STAGES3_LIB another build of the third stages library; without it the file beside the first library
+STAGES3_LIB_PATH = os.environ.get("PDS_AMD_STAGES3_LIB") or os.path.join(os.path.dirname(LIB_PATH),
+                                                                         "libpds_amd_stages3.so")
 
 PDS_OK = 0
 
@@ -306,9 +310,36 @@ STAGES2_SIGNATURES = {
     "pds_multistream_pcen_f64": (c_int32, _MS_PCEN_ARGS),
 }
 
+_SPECAUG_MEAN_ARGS = [
+    c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,  # d_in, in_stride, d_row_off, d_nrows, B, C, d_mean, stream
+]
+_SPECAUG_APPLY_ARGS = [
+    c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32,  # d_in, in_stride, d_row_off, d_nrows, B, C
+    c_void_p, c_int32, c_int32, c_void_p, c_double,  # d_plan, freq_masks, time_masks, d_mean_or_null, fill
+    c_void_p, c_int64, c_int64, c_void_p,  # d_out, out_stride, max_rows, stream
+]
+
+# name -> (restype, argtypes); every symbol include/pds_amd_stages3.h declares
+STAGES3_SIGNATURES = {
+    "pds_stages3_version": (c_int32, []),
+    "pds_stages3_last_error": (c_char_p, []),
+    "pds_specaug_tile_rows": (c_int32, []),
+    "pds_specaug_plan": (
+        c_int32,
+        [c_void_p, c_void_p, c_int32, c_int32,  # d_nrows, d_keys, B, C
+         c_int32, c_int64, c_int32, c_int64, c_double, c_int64,  # freq_masks, freq_width, time_masks, time_width, time_ratio, warp
+         c_void_p, c_void_p],  # d_plan, stream
+    ),
+    "pds_specaug_mean_rows_f32": (c_int32, _SPECAUG_MEAN_ARGS),
+    "pds_specaug_mean_rows_f64": (c_int32, _SPECAUG_MEAN_ARGS),
+    "pds_specaug_apply_rows_f32": (c_int32, _SPECAUG_APPLY_ARGS),
+    "pds_specaug_apply_rows_f64": (c_int32, _SPECAUG_APPLY_ARGS),
+}
+
 _lib = None
 _stages_lib = None
 _stages2_lib = None
+_stages3_lib = None
 
 
 def lib() -> ctypes.CDLL:
@@ -380,6 +411,28 @@ def stages2_lib() -> ctypes.CDLL:
     return _stages2_lib
 
 
+def stages3_lib() -> ctypes.CDLL:
+    """The loaded third stages library; raises :class:`NativeError` if it has not been built"""
+    global _stages3_lib
+    if _stages3_lib is None:
+        if not os.path.exists(STAGES3_LIB_PATH):
+            raise NativeError(
+                f"{STAGES3_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
+                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
+            )
+        try:  # (torch's HIP runtime first, as for lib())
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        loaded = ctypes.CDLL(STAGES3_LIB_PATH)
+        for name, (restype, argtypes) in STAGES3_SIGNATURES.items():
+            fn = getattr(loaded, name)  # AttributeError if the .so is stale
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _stages3_lib = loaded
+    return _stages3_lib
+
+
 def last_error() -> str:
     return lib().pds_last_error().decode("utf-8", "replace")
 
@@ -407,6 +460,15 @@ def check_stages2(rc: int, what: str) -> None:
     """:func:`check` for a call into the second stages library, which keeps its own error string"""
     if rc != PDS_OK:
         msg = stages2_lib().pds_stages2_last_error().decode("utf-8", "replace")
+        if rc == -1:
+            raise ValueError(f"{what}: {msg}")
+        raise NativeError(f"{what}: {msg} (code {rc})")
+
+
+def check_stages3(rc: int, what: str) -> None:
+    """:func:`check` for a call into the third stages library, which keeps its own error string"""
+    if rc != PDS_OK:
+        msg = stages3_lib().pds_stages3_last_error().decode("utf-8", "replace")
         if rc == -1:
             raise ValueError(f"{what}: {msg}")
         raise NativeError(f"{what}: {msg} (code {rc})")

@@ -22,7 +22,11 @@ Same command line and on-disk result as the reference's tool -- a text map of
   ``SlidingCMVN`` -- ``{"name": "sliding_cmvn", "cmn_window": 600}`` -- normalises every utterance by itself in one
   launch over the packed rows, ``SlidingCMVN.apply_rows``; a ``PCEN`` -- ``{"name": "pcen", "smooth": 0.025}``, behind
   a computer with ``"use_log": false`` -- normalises every utterance by itself over the packed rows where they stand,
-  ``PCEN.apply_rows``, and a computer that takes logs is a ``ValueError``; an ``EnergyVAD`` -- ``{"name": "vad"}`` -- decides and
+  ``PCEN.apply_rows``, and a computer that takes logs is a ``ValueError``; a ``SpecAugment`` -- ``{"name":
+  "specaugment", "warp": 5, "fill": "mean"}`` -- warps and masks every utterance by itself over the packed rows where
+  they stand, ``SpecAugment.apply_rows``, seeded per utterance with ``seed + index`` like the dither, so the files do
+  not depend on how the corpus was batched; it is there to write augmented copies of a corpus, reproducibly (``--seed
+  1``, ``--seed 2``, ... give one copy each), and it may stand behind a ``vad`` with ``select_last``; an ``EnergyVAD`` -- ``{"name": "vad"}`` -- decides and
   drops the unvoiced rows of every utterance on the device, ``EnergyVAD.apply_rows``, and the stages behind it see
   the shorter utterances; with ``"select_last": true`` it decides where it stands, the later stages see all frames
   and the rows are dropped after the last stage -- Kaldi's order, ``[{"name": "mfcc", "energy": true}, {"name":
@@ -48,7 +52,8 @@ import numpy as np
 
 from .alias import alias_factory_subclass_from_arg
 from .compute import FrameComputer
-from .post import PCEN, Cepstra, Deltas, EnergyVAD, PostProcessor, SlidingCMVN, Stack, Standardize, refuse_log_computer
+from .post import (PCEN, Cepstra, Deltas, EnergyVAD, PostProcessor, SlidingCMVN, SpecAugment, Stack, Standardize,
+                   refuse_log_computer)
 from .pre import Dither, Preemphasize, PreProcessor, Resample
 from .util import SIGNAL_SOURCES, read_signal
 
@@ -166,7 +171,7 @@ class FeatureDirWriter:
         kinds = {s.dtype for s in signals}
         if len(kinds) > 1:  # (a batch of PCM and float files)
             signals = [s.astype(self.dtype, copy=False) for s in signals]
-        through_feed = self._process_through_feed(signals, lengths)
+        through_feed = self._process_through_feed(signals, lengths, first_index)
         if through_feed is not None:
             return through_feed
         host = np.concatenate(signals) if offsets[-1] else np.zeros(0, self.dtype)
@@ -194,11 +199,11 @@ class FeatureDirWriter:
         else:
             kwargs = {"preemphasis": fused} if fused else {}
             feats, rows = self.computer.compute_packed(packed, offsets[:-1], lengths, **kwargs)
-        feats, rows = self._postprocess(feats, np.asarray(rows, dtype=np.int64))
+        feats, rows = self._postprocess(feats, np.asarray(rows, dtype=np.int64), first_index=first_index)
         feats = feats.to(torch.float32).cpu()
         return [feats[rows[b] : rows[b + 1]].clone() for b in range(len(signals))]
 
-    def _process_through_feed(self, signals, lengths):
+    def _process_through_feed(self, signals, lengths, first_index=0):
         """The batch through the pinned staging ring (``feed.HostFeed``) when the chain allows: an STFT computer
         with a fused kernel, float32 precision, no pre-processor but a pre-emphasis (which rides along with the frame
         loads); else ``None``"""
@@ -239,7 +244,7 @@ class FeatureDirWriter:
         out_rows = {}
 
         def post(feats, row_offsets):
-            feats, rows = self._postprocess(feats, np.asarray(row_offsets, dtype=np.int64))
+            feats, rows = self._postprocess(feats, np.asarray(row_offsets, dtype=np.int64), first_index=first_index)
             out_rows["rows"] = rows
             return feats
 
@@ -250,9 +255,10 @@ class FeatureDirWriter:
         rows = out_rows["rows"] if self.post else own_rows
         return [feats[rows[b] : rows[b + 1]].clone() for b in range(len(signals))]
 
-    def _postprocess(self, feats, rows, probe=False):
+    def _postprocess(self, feats, rows, probe=False, first_index=0):
         """`feats`, `rows` through the post-processors in order.  `probe`: a selection keeps every row (the widest
-        result the chain can give: what sizes a buffer)"""
+        result the chain can give: what sizes a buffer).  `first_index`: the index of the batch's first utterance in
+        the run, which seeds a ``SpecAugment`` as it seeds the dither"""
         import torch
 
         pending = None  # (the EnergyVAD with select_last, its mask, the row offsets the mask goes with)
@@ -267,7 +273,7 @@ class FeatureDirWriter:
                 pending = (post, voiced, rows)
                 continue
             before = rows
-            feats, rows = self._postprocess_one(post, feats, rows, probe)
+            feats, rows = self._postprocess_one(post, feats, rows, probe, first_index)
             if pending is not None:
                 if not np.array_equal(np.diff(rows), np.diff(before)):
                     raise ValueError(
@@ -290,7 +296,7 @@ class FeatureDirWriter:
 
         return feats if feats.dtype in (torch.float32, torch.float64) else feats.to(torch.float64)
 
-    def _postprocess_one(self, post, feats, rows, probe):
+    def _postprocess_one(self, post, feats, rows, probe, first_index=0):
         """one post-processor over the packed rows: ``(feats, rows)``"""
         import torch
 
@@ -299,6 +305,12 @@ class FeatureDirWriter:
                 return feats, rows
             # decided and dropped where it stands: the stages behind it see the shorter utterances
             return post.apply_rows(self._vad_rows(feats), rows)
+        if isinstance(post, SpecAugment):
+            if probe:
+                return feats, rows  # (shapes stay as they are: nothing to size)
+            # every utterance under its own key, seed + its index in the run: the same file however it was batched
+            seeds = [self.seed + first_index + b for b in range(len(rows) - 1)]
+            return post.apply_rows(self._vad_rows(feats), rows, seeds=seeds), rows
         if isinstance(post, Stack) and post.time_axis in (0, -2) and feats.dtype == torch.float32:
             try:
                 return post.apply_rows(feats, rows)

@@ -1,5 +1,5 @@
 """Post-processors on the hot path: ``Deltas``, ``Standardize`` / ``CMVN``, ``Cepstra``, ``SlidingCMVN``, ``EnergyVAD``,
-``PCEN``.
+``PCEN``, ``SpecAugment``.
 
 Same classes, aliases, arguments and error behaviour as the reference's (post.py:38-491);
 the element-wise and stencil arithmetic runs in HIP kernels (``csrc/post.hip``) -- there
@@ -20,6 +20,10 @@ over a packed ragged batch.
 smoother per column and a root compression, two HIP kernels of the second stages library (``csrc/pcen.hip``) over a
 packed ragged batch.
 
+``SpecAugment`` is not in the reference either: a time warp, frequency masks and time masks over the feature matrix
+for training, drawn from a counter-based generator keyed per utterance, three HIP kernels of the third stages library
+(``csrc/specaug.hip``) over a packed ragged batch.
+
 ``Stack`` moves data only: views for a single tensor, one copy
 kernel for a packed ragged batch.  CMVN statistics files (``rfilename``, ``save``) go through
 ``util.read_signal`` / numpy.
@@ -31,9 +35,11 @@ from typing import Callable, Optional, Tuple, Union
 import numpy as np
 
 from . import _native
+from . import pre as _pre
 from .alias import AliasedFactory
 
-__all__ = ["CMVN", "Cepstra", "Deltas", "EnergyVAD", "PCEN", "PostProcessor", "SlidingCMVN", "Stack", "Standardize"]
+__all__ = ["CMVN", "Cepstra", "Deltas", "EnergyVAD", "PCEN", "PostProcessor", "SlidingCMVN", "SpecAugment", "Stack",
+           "Standardize"]
 
 
 class PostProcessor(AliasedFactory):
@@ -1349,7 +1355,7 @@ class PCEN(PostProcessor):
     # ---- arrays and tensors ---------------------------------------------------------
 
     @staticmethod
-    def _device_rows(features, axis):
+    def _device_rows(features, axis, who="PCEN"):
         """`features` on the device as ``(B * T, C)`` rows with time in front of the columns -> (on_gpu, features, rows,
         B, T, the shape with time moved to -2)"""
         on_gpu = _is_gpu_tensor(features)
@@ -1357,7 +1363,7 @@ class PCEN(PostProcessor):
             features = np.asarray(features)
         shape = tuple(features.shape)
         if len(shape) not in (2, 3):
-            raise ValueError("PCEN: expected a 2-D or 3-D array or tensor")
+            raise ValueError(f"{who}: expected a 2-D or 3-D array or tensor")
         axis = axis % len(shape)
         torch = _native.require_device()
         if on_gpu:
@@ -1386,14 +1392,326 @@ class PCEN(PostProcessor):
     def apply(self, features, axis: int = -1, in_place: bool = False):
         on_gpu, features, rows, B, T, lead = self._device_rows(features, axis)
         out = self.apply_rows(rows, np.arange(B + 1, dtype=np.int64) * T)
-        out = out.reshape(lead).movedim(-2, axis % len(lead))
-        if on_gpu:
-            if in_place and features.dtype == out.dtype:
-                features.copy_(out)
-                return features
-            return out
-        res = out.cpu().numpy()
-        if in_place and features.dtype == res.dtype and features.flags.writeable:
-            features[...] = res
+        return _finish_rows(out, lead, axis, on_gpu, features, in_place)
+
+
+def _finish_rows(out, lead, axis, on_gpu, features, in_place):
+    """the packed result `out` of ``PCEN._device_rows``'s rows in `features`' shape and kind"""
+    out = out.reshape(lead).movedim(-2, axis % len(lead))
+    if on_gpu:
+        if in_place and features.dtype == out.dtype:
+            features.copy_(out)
             return features
-        return res
+        return out
+    res = out.cpu().numpy()
+    if in_place and features.dtype == res.dtype and features.flags.writeable:
+        features[...] = res
+        return features
+    return res
+
+
+# ------------------------------------------------------------------ SpecAugment ------
+
+_SPECAUG_TILE = 32  # rows of a block's tile of pds_specaug_apply_rows (pds_specaug_tile_rows, csrc/specaug_rule.h)
+_SPECAUG_MAX_BLOCKS = (1 << 31) - 1  # ... and the blocks one call of it may launch
+_SPECAUG_MAX_MASKS = 16
+_SPECAUG_MAX_WIDTH = (1 << 31) - 2
+_SPECAUG_MAX_WARP = 1 << 29
+_SPECAUG_MAX_ROWS = (1 << 31) - 1  # rows of an utterance the draws are defined for
+
+
+def _specaug_int(value, what, hi):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise ValueError(f"SpecAugment: {what} must be an integer, got {value!r}")
+    value = int(value)
+    if not 0 <= value <= hi:
+        raise ValueError(f"SpecAugment: {what} must lie in [0, {hi}], got {value!r}")
+    return value
+
+
+def _specaug_spans(nrows, limit=None):
+    """``[(lo, hi, max_rows), ...]``: the batch cut into launches of at most `limit` blocks each, one block per
+    (utterance, tile of ``_SPECAUG_TILE`` rows of the span's longest utterance).  Greedy and in order; an utterance of
+    fewer than 2^31 rows always fits a launch of its own"""
+    limit = _SPECAUG_MAX_BLOCKS if limit is None else limit
+    if len(nrows) and len(nrows) * -(-int(np.max(nrows)) // _SPECAUG_TILE) <= limit:
+        return [(0, len(nrows), int(np.max(nrows)))]  # (what nearly every batch is: one launch)
+    spans, lo, longest = [], 0, 0
+    for b, n in enumerate(int(n) for n in nrows):
+        grown = max(longest, n)
+        if b > lo and (b + 1 - lo) * -(-grown // _SPECAUG_TILE) > limit:
+            spans.append((lo, b, longest))
+            lo, grown = b, n
+        longest = grown
+    if len(nrows) > lo:
+        spans.append((lo, len(nrows), longest))
+    return spans
+
+
+class SpecAugment(PostProcessor):
+    """SpecAugment (Park et al. 2019): a time warp, frequency masks and time masks over a feature matrix, for training
+
+    `axis` of :func:`apply` is the *time* axis; the last remaining axis holds the columns.  The draws come from a
+    counter-based generator keyed per utterance, as ``pre.Dither``'s noise does: an utterance's result depends on its key
+    and nothing else, whatever the batch it stands in.  `seed` works as in ``Dither``: the object holds a state, and every
+    utterance it augments without explicit seeds advances it.
+
+    The definition.
+
+    Per utterance of T ≥ 1 rows and C ≥ 1 columns with a 64-bit key k:
+
+    0. Generator.
+       - `P(i, d)` is one Philox4x32-10 block with counter words `(i, 0, d, 0)` and key words `(k mod 2³², k >> 32)`.
+         Its output words are `r0..r3`. The round function is the one `csrc/dither_noise.h` already has.
+       - `U(r, n) = (uint64(r) · uint64(n + 1)) >> 32` for 0 ≤ n < 2³¹. It is an integer in [0, n].
+    1. Warp.
+       - If `warp = W ≥ 1` and `T ≥ 2W + 3`, let `r = P(0, 1)`.
+       - `w0 = W + 1 + U(r0, T − 3 − 2W)`.
+       - `w1 = w0 − W + U(r1, 2W)`.
+       - Then `W + 1 ≤ w0 ≤ T − 2 − W` and `1 ≤ w1 ≤ T − 2`.
+       - Otherwise `w0 = w1 = −1` (no warp).
+    2. Frequency mask j, 0 ≤ j < freq_masks.
+       - `r = P(j, 2)`.
+       - `f = U(r0, min(freq_width, C))`.
+       - `f0 = U(r1, C − f)`.
+       - The mask covers columns `[f0, f0 + f)`.
+    3. Time mask j, 0 ≤ j < time_masks.
+       - `b = min(time_width, (int64) floor(time_ratio · (double) T))`, the product rounded once.
+       - `r = P(j, 3)`.
+       - `t = U(r0, b)`.
+       - `t0 = U(r1, T − t)`.
+       - The mask covers rows `[t0, t0 + t)`.
+    4. Warped value `v[t][c]`.
+       - Without a warp, `v[t][c]` is `x[t][c]`, copied.
+       - With one, the source position is float64 with every operation rounded by itself (no contraction):
+         - for `t ≤ w1`: `s = ((double) t · (double) w0) / (double) w1`
+         - for `t > w1`: `s = (double) w0 + ((double)(t − w1) · (double)(T − 1 − w0)) / (double)(T − 1 − w1)`
+       - `i = floor(s)` and `a = s − i`.
+       - If `a == 0`, the value is `x[i][c]`, copied.
+       - Otherwise the value is `x[i][c] + a · (x[i+1][c] − x[i][c])`, with the samples widened exactly, the
+         difference, product and sum each rounded once, and the result rounded once to the row type.
+       - I checked on the CPU for every T < 60, W < 8 and every admissible (w0, w1) that:
+         - s is strictly increasing,
+         - s(0) = 0, s(w1) = w0 and s(T − 1) = T − 1 exactly,
+         - `i + 1 ≤ T − 1` whenever `a > 0`.
+    5. Mean (only for `fill="mean"`).
+       - It is taken over the utterance's T · C input elements in float64, as 64 interleaved partial sums.
+       - `p_j` sums the elements with flat index `e = t · C + c ≡ j (mod 64)`, in ascending e, starting from +0.0.
+       - `s = ((+0.0 + p_0) + p_1) + … + p_63`.
+       - `m = s / (double)(T · C)`.
+       - This is the rule and the reason of §4.8. Lane j of one wave owns `p_j`, and the host restates it in a few
+         lines.
+    6. Output.
+       - `out[t][c]` is the fill value, rounded once to the row type, if c lies in any frequency mask or t in any time
+         mask.
+       - Otherwise `out[t][c]` is `v[t][c]`.
+       - T = 0 gives nothing.
+
+    The plan (steps 1 to 3) is integers only.  Unmasked values without a warp, or at ``a == 0``, are copies, byte for
+    byte: NaN payloads and signed zeros pass.  Everything else is plain IEEE float64 arithmetic, which numpy reproduces
+    bit for bit; a computed NaN (such as inf - inf in the interpolation) is only promised to be a NaN.  Anything but
+    float32 and float64 input is widened to float64 first.  An utterance of 2^31 rows or more is a ``ValueError``.
+
+    Not a stage of batched streaming: a time mask's bound and the warp need T, and augmentation is a training-time
+    stage.
+    """
+
+    aliases = {"specaugment", "spec_augment", "specaug"}
+
+    def __init__(self, freq_masks: int = 2, freq_width: int = 10, time_masks: int = 2, time_width: int = 50,
+                 time_ratio: float = 1.0, warp: int = 0, fill: Union[float, str] = 0.0, seed: Optional[int] = None):
+        self.freq_masks = _specaug_int(freq_masks, "freq_masks", _SPECAUG_MAX_MASKS)
+        self.freq_width = _specaug_int(freq_width, "freq_width", _SPECAUG_MAX_WIDTH)
+        self.time_masks = _specaug_int(time_masks, "time_masks", _SPECAUG_MAX_MASKS)
+        self.time_width = _specaug_int(time_width, "time_width", _SPECAUG_MAX_WIDTH)
+        if isinstance(time_ratio, (bool, np.bool_)) or not isinstance(time_ratio, (int, float, np.integer, np.floating)):
+            raise ValueError(f"SpecAugment: time_ratio must be a number, got {time_ratio!r}")
+        self.time_ratio = float(time_ratio)
+        if not 0.0 < self.time_ratio <= 1.0:
+            raise ValueError(f"SpecAugment: time_ratio must lie in (0, 1], got {time_ratio!r}")
+        self.warp = _specaug_int(warp, "warp", _SPECAUG_MAX_WARP)
+        if isinstance(fill, str):
+            if fill != "mean":
+                raise ValueError(f'SpecAugment: fill must be a number or "mean", got {fill!r}')
+            self.fill = "mean"
+        elif isinstance(fill, (bool, np.bool_)) or not isinstance(fill, (int, float, np.integer, np.floating)):
+            raise ValueError(f'SpecAugment: fill must be a number or "mean", got {fill!r}')
+        else:
+            self.fill = float(fill)  # (finite or not: a NaN or an infinity marks the masked elements as well)
+        if seed is not None and (isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer))
+                                 or int(seed) < 0):
+            raise ValueError(f"SpecAugment: seed must be None or a non-negative integer, got {seed!r}")
+        self._given_seed = seed
+        self._seed = _pre._seed_state(seed)
+
+    @property
+    def seed(self) -> Optional[int]:
+        """the `seed` this object was built with"""
+        return self._given_seed
+
+    @property
+    def plan_words(self) -> int:
+        """int64 words of an utterance's plan: ``w0, w1``, ``(f0, f)`` per frequency mask, ``(t0, t)`` per time mask"""
+        return 2 + 2 * self.freq_masks + 2 * self.time_masks
+
+    def __repr__(self) -> str:
+        # (what the object was built with and nothing of its state: a test id made of it is the same in every run)
+        return (f"SpecAugment(freq_masks={self.freq_masks!r}, freq_width={self.freq_width!r}, "
+                f"time_masks={self.time_masks!r}, time_width={self.time_width!r}, time_ratio={self.time_ratio!r}, "
+                f"warp={self.warp!r}, fill={self.fill!r}, seed={self._given_seed!r})")
+
+    def _keys(self, B, seeds):
+        """one uint64 key per utterance: of `seeds` by ``Dither``'s rule, else the next B of the object's sequence"""
+        if seeds is None:
+            keys = np.empty(B, dtype=np.uint64)
+            for b in range(B):
+                self._seed = _pre._next_key(self._seed)
+                keys[b] = self._seed
+            return keys
+        if len(seeds) != B:
+            raise ValueError("SpecAugment: one seed per utterance")
+        return _pre.dither_keys(seeds)
+
+    # ---- packed ragged batches ------------------------------------------------------
+
+    @staticmethod
+    def _check_counts(nrows, C):
+        nrows = np.ascontiguousarray(nrows, dtype=np.int64).reshape(-1)
+        if isinstance(C, (bool, np.bool_)) or not isinstance(C, (int, np.integer)) or not 1 <= int(C) <= (1 << 31) - 1:
+            raise ValueError(f"SpecAugment: C must be an integer in [1, 2^31 - 1], got {C!r}")
+        if len(nrows) > (1 << 31) - 1:
+            raise ValueError("SpecAugment: too many utterances")
+        if len(nrows) and (nrows.min() < 0 or nrows.max() > _SPECAUG_MAX_ROWS):
+            raise ValueError("SpecAugment: an utterance's row count must lie in [0, 2^31 - 1]")
+        return nrows, int(C)
+
+    def _plan_into(self, torch, lib, d_nrows, d_keys, B, C, device):
+        """the plan kernel over B utterances whose counts and keys are on the device: an int64 ``(B, plan_words)``"""
+        plan = torch.empty((B, self.plan_words), dtype=torch.int64, device=device)
+        if B:
+            with torch.cuda.device(device):
+                rc = lib.pds_specaug_plan(d_nrows.data_ptr(), d_keys.data_ptr(), B, C, self.freq_masks, self.freq_width,
+                                          self.time_masks, self.time_width, self.time_ratio, self.warp, plan.data_ptr(),
+                                          torch.cuda.current_stream(device).cuda_stream)
+            _native.check_stages3(rc, "pds_specaug_plan")
+        return plan
+
+    def plan_rows(self, nrows, C, seeds=None, device=None):
+        """The plans of B utterances of ``nrows[b]`` rows and `C` columns (steps 1 to 3 of the definition): an int64 GPU
+        tensor ``(B, 2 + 2 * freq_masks + 2 * time_masks)`` of ``w0, w1``, ``(f0, f)`` per frequency mask and ``(t0,
+        t)`` per time mask.  With `seeds`, one integer per utterance, utterance b gets the plan of the first ``apply``
+        of ``SpecAugment(..., seed=seeds[b])`` and this object's sequence is left alone; with ``seeds=None`` the
+        sequence advances once per utterance, in order.  What :func:`apply_rows` takes as `plan`"""
+        torch = _native.require_device()
+        lib = _native.stages3_lib()
+        nrows, C = self._check_counts(nrows, C)
+        B = len(nrows)
+        keys = self._keys(B, seeds)
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        table = torch.from_numpy(np.stack([nrows, keys.view(np.int64)])).to(device)  # counts and keys in one copy
+        return self._plan_into(torch, lib, table[0], table[1], B, C, device)
+
+    def mean_rows(self, feats, row_offsets):
+        """The mean of every utterance of a packed ragged batch (step 5 of the definition): a float64 GPU tensor
+        ``(B,)``, NaN for an empty utterance.  `feats` and `row_offsets` as :func:`apply_rows` takes them"""
+        torch = _native.require_device()
+        lib = _native.stages3_lib()
+        feats, rows, stride = PCEN._check_rows(torch, feats, row_offsets)
+        B, C = len(rows) - 1, feats.shape[1]
+        self._check_counts(np.diff(rows), max(C, 1))
+        mean = torch.empty((B,), dtype=torch.float64, device=feats.device)
+        if B and C == 0:
+            mean.fill_(float("nan"))
+        elif B:
+            meta, _ = _rows_meta(rows, feats.device)
+            self._mean_into(torch, lib, feats, stride, meta[0], meta[1], B, mean)
+        return mean
+
+    @staticmethod
+    def _mean_into(torch, lib, feats, stride, d_row_off, d_nrows, B, mean):
+        fn = lib.pds_specaug_mean_rows_f32 if feats.dtype == torch.float32 else lib.pds_specaug_mean_rows_f64
+        with torch.cuda.device(feats.device):
+            rc = fn(feats.data_ptr(), stride, d_row_off.data_ptr(), d_nrows.data_ptr(), B, feats.shape[1],
+                    mean.data_ptr(), _stream(torch, feats))
+        _native.check_stages3(rc, "pds_specaug_mean_rows")
+
+    def _apply_into(self, fn, nrows, C, d_in, in_stride, d_row_off, d_nrows, d_plan, d_mean, d_out, out_stride, stream):
+        """the apply kernel's launches over the checked batch, every array by its address: one launch, unless the batch
+        needs more blocks (utterances x tiles of the longest) than a grid holds; then span by span"""
+        for lo, hi, longest in _specaug_spans(nrows, _SPECAUG_MAX_BLOCKS):
+            rc = fn(d_in, in_stride, d_row_off + 8 * lo, d_nrows + 8 * lo, hi - lo, C,
+                    d_plan + 8 * self.plan_words * lo, self.freq_masks, self.time_masks,
+                    (d_mean + 8 * lo) if d_mean else None, 0.0 if self.fill == "mean" else self.fill, d_out, out_stride,
+                    longest, stream)
+            _native.check_stages3(rc, "pds_specaug_apply_rows")
+
+    def apply_rows(self, feats, row_offsets, seeds=None, plan=None, out=None):
+        """Every utterance of a packed ragged batch augmented by itself on the GPU: one upload of offsets, counts and
+        keys, then two launches (three with ``fill="mean"``), no host synchronisation
+
+        `feats`: ``(total_rows, C)`` float32 or float64 GPU tensor (rows may be strided: a column slice of a wider
+        tensor), utterance b in rows ``row_offsets[b]:row_offsets[b+1]``; empty utterances are allowed.  `seeds` as
+        :func:`plan_rows` takes them.  `plan`: the tensor a previous :func:`plan_rows` returned, in place of drawing one
+        (the same masks on two views of an utterance; any plan a caller writes: a warp centre outside ``[1, T - 2]`` is
+        no warp); `plan` together with `seeds` is a ``ValueError``, and with `plan` the object's sequence is left alone.
+        Returns a tensor of the same shape and dtype (`out`, if given; it may be `feats` itself only where ``warp ==
+        0``: a warped row reads its neighbours).  Rows outside ``row_offsets[0]:row_offsets[-1]`` are not written.
+        """
+        if plan is not None and seeds is not None:
+            raise ValueError("SpecAugment: plan and seeds together: the plan holds what the seeds would draw")
+        if out is not None and out is feats and self.warp > 0:
+            raise ValueError("SpecAugment: out is feats under warp > 0: a warped row reads its neighbours")
+        torch = _native.require_device()
+        lib = _native.stages3_lib()
+        feats, rows, stride = PCEN._check_rows(torch, feats, row_offsets)
+        R, C = feats.shape
+        B = len(rows) - 1
+        nrows, _ = self._check_counts(np.diff(rows), max(C, 1))
+        if seeds is not None and len(seeds) != B:
+            raise ValueError("SpecAugment: one seed per utterance")
+        if out is None:
+            out = torch.empty((R, C), dtype=feats.dtype, device=feats.device)
+        elif (not _is_gpu_tensor(out) or out.dtype != feats.dtype or out.device != feats.device
+              or tuple(out.shape) != (R, C) or (C and out.stride(1) != 1)):
+            raise ValueError("out must be a GPU tensor of feats' shape, dtype and device with contiguous rows")
+        out_stride = out.stride(0) if R > 1 else C
+        if out_stride < C:
+            raise ValueError("rows of out must not overlap")
+        if self.warp > 0 and R and C and out.data_ptr() == feats.data_ptr():
+            raise ValueError("SpecAugment: out shares feats' memory under warp > 0: a warped row reads its neighbours")
+        if plan is not None:
+            if (not _is_gpu_tensor(plan) or plan.dtype != torch.int64 or plan.device != feats.device
+                    or tuple(plan.shape) != (B, self.plan_words) or not plan.is_contiguous()):
+                raise ValueError(f"plan must be a contiguous int64 GPU tensor ({B}, {self.plan_words}) on feats' device")
+            keys = None
+        else:
+            keys = self._keys(B, seeds)
+        if B == 0 or R == 0 or C == 0 or rows[-1] == rows[0]:
+            return out
+        if keys is None:
+            meta, _ = _rows_meta(rows, feats.device)
+        else:  # offsets, counts and keys go up in one copy (a key's bits travel as int64)
+            meta = torch.from_numpy(np.stack([rows[:-1], nrows, keys.view(np.int64)])).to(feats.device)
+            plan = self._plan_into(torch, lib, meta[1], meta[2], B, C, feats.device)
+        mean = None
+        if self.fill == "mean":
+            mean = torch.empty((B,), dtype=torch.float64, device=feats.device)
+            self._mean_into(torch, lib, feats, stride, meta[0], meta[1], B, mean)
+        fn = lib.pds_specaug_apply_rows_f32 if feats.dtype == torch.float32 else lib.pds_specaug_apply_rows_f64
+        with torch.cuda.device(feats.device):
+            self._apply_into(fn, nrows, C, feats.data_ptr(), stride, meta[0].data_ptr(), meta[1].data_ptr(),
+                             plan.data_ptr(), mean.data_ptr() if mean is not None else 0, out.data_ptr(), out_stride,
+                             _stream(torch, feats))
+        return out
+
+    # ---- arrays and tensors ---------------------------------------------------------
+
+    def apply(self, features, axis: int = -2, in_place: bool = False):
+        """`features` augmented: 2-D, or 3-D where each slice along the remaining leading axis is an utterance of its
+        own with the next key of the sequence.  `axis` is the time axis, the last remaining axis the columns.  A numpy
+        array gives an array, a GPU tensor a tensor.  `in_place` only where ``warp == 0``"""
+        if in_place and self.warp > 0:
+            raise ValueError("SpecAugment: in_place under warp > 0: a warped row reads its neighbours")
+        on_gpu, features, rows, B, T, lead = PCEN._device_rows(features, axis, "SpecAugment")
+        out = self.apply_rows(rows, np.arange(B + 1, dtype=np.int64) * T)
+        return _finish_rows(out, lead, axis, on_gpu, features, in_place)
