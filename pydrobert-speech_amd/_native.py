@@ -1,7 +1,8 @@
 """ctypes binding of ``libpds_amd.so`` (C ABI: ``include/pds_amd.h``), of ``libpds_amd_stages.so``, the stage
 kernels outside the fused kernel's instantiation matrix (C ABI: ``include/pds_amd_stages.h``), of
-``libpds_amd_stages2.so``, the second capped library of stage kernels (C ABI: ``include/pds_amd_stages2.h``), and of
-``libpds_amd_stages3.so``, the third (C ABI: ``include/pds_amd_stages3.h``).
+``libpds_amd_stages2.so``, the second capped library of stage kernels (C ABI: ``include/pds_amd_stages2.h``), of
+``libpds_amd_stages3.so``, the third (C ABI: ``include/pds_amd_stages3.h``), and of ``libpds_amd_stages4.so``, the
+fourth (C ABI: ``include/pds_amd_stages4.h``).
 
 There is deliberately no fallback: if the shared library is missing or a compute call
 is made without a HIP device, an exception is raised.  Nothing in this package computes
@@ -22,6 +23,9 @@ STAGES2_LIB_PATH = os.environ.get("PDS_AMD_STAGES2_LIB") or os.path.join(os.path
 # ... and PDS_AMD_STAGES3_LIB another build of the third stages library; without it the file beside the first library
 STAGES3_LIB_PATH = os.environ.get("PDS_AMD_STAGES3_LIB") or os.path.join(os.path.dirname(LIB_PATH),
                                                                          "libpds_amd_stages3.so")
+# ... and PDS_AMD_STAGES4_LIB another build of the fourth stages library; without it the file beside the first library
+STAGES4_LIB_PATH = os.environ.get("PDS_AMD_STAGES4_LIB") or os.path.join(os.path.dirname(LIB_PATH),
+                                                                         "libpds_amd_stages4.so")
 
 PDS_OK = 0
 
@@ -336,10 +340,27 @@ STAGES3_SIGNATURES = {
     "pds_specaug_apply_rows_f64": (c_int32, _SPECAUG_APPLY_ARGS),
 }
 
+_PLP_ROWS_ARGS = [
+    c_void_p, c_int64, c_int64, c_int32, c_int32,  # d_in, in_stride, R, F, copy
+    c_void_p, c_void_p, c_void_p, c_int32, c_int32,  # d_w, d_B, d_L, p, K
+    c_double, c_double, c_void_p, c_int64, c_void_p, c_void_p,  # compress_factor, floor, d_out, out_stride, d_aux_or_null, stream
+]
+
+# name -> (restype, argtypes); every symbol include/pds_amd_stages4.h declares
+STAGES4_SIGNATURES = {
+    "pds_stages4_version": (c_int32, []),
+    "pds_stages4_last_error": (c_char_p, []),
+    "pds_plp_block_rows": (c_int32, []),
+    "pds_plp_lds_bytes": (c_int64, [c_int32]),
+    "pds_plp_rows_f32": (c_int32, _PLP_ROWS_ARGS),
+    "pds_plp_rows_f64": (c_int32, _PLP_ROWS_ARGS),
+}
+
 _lib = None
 _stages_lib = None
 _stages2_lib = None
 _stages3_lib = None
+_stages4_lib = None
 
 
 def lib() -> ctypes.CDLL:
@@ -433,6 +454,28 @@ def stages3_lib() -> ctypes.CDLL:
     return _stages3_lib
 
 
+def stages4_lib() -> ctypes.CDLL:
+    """The loaded fourth stages library; raises :class:`NativeError` if it has not been built"""
+    global _stages4_lib
+    if _stages4_lib is None:
+        if not os.path.exists(STAGES4_LIB_PATH):
+            raise NativeError(
+                f"{STAGES4_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
+                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
+            )
+        try:  # (torch's HIP runtime first, as for lib())
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        loaded = ctypes.CDLL(STAGES4_LIB_PATH)
+        for name, (restype, argtypes) in STAGES4_SIGNATURES.items():
+            fn = getattr(loaded, name)  # AttributeError if the .so is stale
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _stages4_lib = loaded
+    return _stages4_lib
+
+
 def last_error() -> str:
     return lib().pds_last_error().decode("utf-8", "replace")
 
@@ -469,6 +512,15 @@ def check_stages3(rc: int, what: str) -> None:
     """:func:`check` for a call into the third stages library, which keeps its own error string"""
     if rc != PDS_OK:
         msg = stages3_lib().pds_stages3_last_error().decode("utf-8", "replace")
+        if rc == -1:
+            raise ValueError(f"{what}: {msg}")
+        raise NativeError(f"{what}: {msg} (code {rc})")
+
+
+def check_stages4(rc: int, what: str) -> None:
+    """:func:`check` for a call into the fourth stages library, which keeps its own error string"""
+    if rc != PDS_OK:
+        msg = stages4_lib().pds_stages4_last_error().decode("utf-8", "replace")
         if rc == -1:
             raise ValueError(f"{what}: {msg}")
         raise NativeError(f"{what}: {msg} (code {rc})")

@@ -22,7 +22,11 @@ Same command line and on-disk result as the reference's tool -- a text map of
   ``SlidingCMVN`` -- ``{"name": "sliding_cmvn", "cmn_window": 600}`` -- normalises every utterance by itself in one
   launch over the packed rows, ``SlidingCMVN.apply_rows``; a ``PCEN`` -- ``{"name": "pcen", "smooth": 0.025}``, behind
   a computer with ``"use_log": false`` -- normalises every utterance by itself over the packed rows where they stand,
-  ``PCEN.apply_rows``, and a computer that takes logs is a ``ValueError``; a ``SpecAugment`` -- ``{"name":
+  ``PCEN.apply_rows``, and a computer that takes logs is a ``ValueError``; a ``PLP`` -- ``{"name": "plp"}``, behind a
+  computer with ``"use_log": false`` too -- turns every row into its PLP cepstra in one launch over the packed rows,
+  takes the centre frequencies and the energy column it leaves open from the computer, and keeps the row counts, so
+  it stands in ``mfcc``'s place in front of ``{"name": "vad", "select_last": true}`` and ``sliding_cmvn``; a
+  ``SpecAugment`` -- ``{"name":
   "specaugment", "warp": 5, "fill": "mean"}`` -- warps and masks every utterance by itself over the packed rows where
   they stand, ``SpecAugment.apply_rows``, seeded per utterance with ``seed + index`` like the dither, so the files do
   not depend on how the corpus was batched; it is there to write augmented copies of a corpus, reproducibly (``--seed
@@ -52,7 +56,7 @@ import numpy as np
 
 from .alias import alias_factory_subclass_from_arg
 from .compute import FrameComputer
-from .post import (PCEN, Cepstra, Deltas, EnergyVAD, PostProcessor, SlidingCMVN, SpecAugment, Stack, Standardize,
+from .post import (PCEN, PLP, Cepstra, Deltas, EnergyVAD, PostProcessor, SlidingCMVN, SpecAugment, Stack, Standardize,
                    refuse_log_computer)
 from .pre import Dither, Preemphasize, PreProcessor, Resample
 from .util import SIGNAL_SOURCES, read_signal
@@ -130,7 +134,12 @@ class FeatureDirWriter:
                 raise NotImplementedError(f"pre-processor {type(pre).__name__}")
         if computer is not None and any(isinstance(post, PCEN) for post in postprocessors):
             refuse_log_computer(computer)  # (PCEN takes linear energies)
-        self.computer, self.pre, self.post = computer, list(preprocessors), list(postprocessors)
+        postprocessors = list(postprocessors)
+        if computer is not None:
+            # a PLP takes linear energies too, and the centre frequencies and the energy column it leaves open are the
+            # computer's
+            postprocessors = [post.bound_to(computer) if isinstance(post, PLP) else post for post in postprocessors]
+        self.computer, self.pre, self.post = computer, list(preprocessors), postprocessors
         self.out_dir, self.channel, self.force_as, self.seed = out_dir, channel, force_as, seed
         self.prefix, self.suffix, self.manifest = file_prefix, file_suffix, manifest
         self.dtype = np.dtype(precision)
@@ -317,6 +326,8 @@ class FeatureDirWriter:
             except ValueError:
                 pass  # a pad mode the row kernel does not have: per utterance below
         elif isinstance(post, Cepstra):
+            return post.apply(feats, axis=-1), rows  # row by row: the whole packed batch in one launch, same rows
+        elif isinstance(post, PLP):
             return post.apply(feats, axis=-1), rows  # row by row: the whole packed batch in one launch, same rows
         elif isinstance(post, SlidingCMVN) and feats.dtype in (torch.float32, torch.float64):
             return post.apply_rows(feats, rows), rows  # every utterance by itself, the packed batch in one launch

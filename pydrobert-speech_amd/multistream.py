@@ -18,6 +18,7 @@ samples of up to `capacity` streams in a device pool and takes every stream that
     sb = StreamBatch(computer, capacity=4096, cepstra=Cepstra(13))  # cepstral coefficients of every row, see below
     sb = StreamBatch(computer, capacity=4096, sliding_cmvn=SlidingCMVN(600, 1))  # sliding-window CMVN, see below
     sb = StreamBatch(computer, capacity=4096, pcen=PCEN())         # per-channel energy normalisation, see below
+    sb = StreamBatch(computer, capacity=4096, plp=PLP())           # PLP cepstra of every row, see below
 
 Every stream gets, call by call, what a private copy of `computer` returns from ``compute_chunk`` / ``finalize`` for
 the same chunks: the same row counts, dtype and -- for float32 and float64 samples -- the same values bit for bit as
@@ -40,7 +41,7 @@ the assemble launch (``compute_chunks`` only), the feature launch, the commit or
 post stages.  A class adds what differs through four hooks: its host state, the order in which the emitting streams
 launch, its extra rows of launch metadata, and the feature launch itself.
 
-The post stages -- pcen, cepstra, cmvn or sliding-window cmvn, deltas, stack, in that order -- are objects of one protocol,
+The post stages -- pcen, cepstra or plp, cmvn or sliding-window cmvn, deltas, stack, in that order -- are objects of one protocol,
 :class:`_Stage`, which the constructor lists and the tick loops over twice.  A stage owns its parsed spec, its host
 state (``DeltaState`` ...; none for cepstra), its device pools, its typed entry point -- looked up when the stage is
 built, so a library without it is an ``AttributeError`` for the batch that asks for the stage and no other -- and the
@@ -139,6 +140,15 @@ a few rows per stream.  The upload grows by the fresh flags, one byte per stream
 stream's rows lie: its id and its first row, a word each (no section of a ``finalize`` tick carries them).
 ``finalize`` returns a stream to fresh.  :func:`StreamBatch.pcen_smooth` reads the streams' current M.
 
+With `plp` (a :class:`post.PLP`, over a computer that does not take logs) every static row becomes its `num_ceps`
+perceptual linear prediction cepstra -- the stage stands in `cepstra`'s place as the first post stage (it excludes
+`cepstra` and `pcen`): one ``pds_plp_rows`` launch of the fourth stages library (``csrc/plp.hip``) over the tick's
+static rows, none in a tick without rows, before `cmvn` / `sliding_cmvn`, `deltas` and `stack`, which see rows of
+width `num_ceps`.  A row depends on nothing but itself, so the stage has no state, no pool and no upload section, and
+the kernel is the one the offline calls launch: a stream's rows are ``stack(deltas(cmvn(plp.apply(statics))))`` of the
+offline objects over its whole utterance, bit for bit, whatever the cuts.  The centre frequencies and the energy column
+are the computer's where the object leaves them open (:func:`post.PLP.bound_to`).
+
 With `stack` (a :class:`post.Stack`: frames along the row axis, ``pad_mode`` None, "edge" or "constant") every
 ``nv = num_vectors`` consecutive rows of a stream become one row of ``nv`` times the width -- the last stage, after
 `cmvn` and `deltas`: a stream's rows, concatenated over its ``compute_chunks`` calls and its ``finalize``, are
@@ -164,11 +174,11 @@ import numpy as np
 from . import _native, config
 from .alias import alias_factory_subclass_from_arg
 from .compute import PackedLayout, ShortTimeFourierTransformFrameComputer
-from .post import PCEN, Cepstra, Deltas, PostProcessor, SlidingCMVN, Stack, Standardize, refuse_log_computer
+from .post import PCEN, PLP, Cepstra, Deltas, PostProcessor, SlidingCMVN, Stack, Standardize, refuse_log_computer
 from .pre import Dither, Preemphasize, PreProcessor, dither_keys
 
 __all__ = ["CmvnState", "DeltaState", "DitherState", "PcenState", "SlidingState", "StackState", "StreamBatch",
-           "StreamState", "streaming_cepstra", "streaming_cmvn", "streaming_deltas", "streaming_dither", "streaming_pcen",
+           "StreamState", "streaming_cepstra", "streaming_cmvn", "streaming_deltas", "streaming_dither", "streaming_pcen", "streaming_plp",
            "streaming_preemphasis", "streaming_sliding_cmvn", "streaming_stack"]
 
 _FIELDS = 8  # int64 per entry of pds_multistream_assemble's metadata (include/pds_amd.h)
@@ -686,6 +696,21 @@ class SlidingState:
         meta[:, 5:] = 0
 
 
+def streaming_plp(plp, computer=None) -> Optional[PLP]:
+    """`plp` as :class:`StreamBatch` takes it -- a :class:`post.PLP` or what
+    ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one (``"plp"``, ``{"name": "plp", "num_ceps": 13}``)
+    -> the ``PLP``, or None for ``plp=None``; ``ValueError`` for anything else.  Given the `computer`, the ``PLP`` bound
+    to it (:func:`post.PLP.bound_to`: centre frequencies and `energy` from the computer where the object leaves them
+    open), a ``ValueError`` for a computer that takes logs and for a width the object refuses"""
+    if plp is None:
+        return None
+    plp = _post_processor("plp", plp, PLP)
+    if computer is not None:
+        plp = plp.bound_to(computer)
+        plp._split(computer.num_coeffs)
+    return plp
+
+
 def streaming_pcen(pcen, computer=None) -> Optional[PCEN]:
     """`pcen` as :class:`StreamBatch` takes it -- a :class:`post.PCEN` or what
     ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one (``"pcen"``, ``{"name": "pcen", "smooth": 0.025}``)
@@ -1018,6 +1043,22 @@ class _CepstraStage(_Stage):
         return self.spec.apply(rows)  # one launch on `stream`, none without rows
 
 
+class _PlpStage(_Stage):
+    """`plp`, a kernel of the fourth stages library, in `cepstra`'s place: a row depends on nothing but itself -- no
+    state, no pool, no section"""
+
+    def __init__(self, batch, spec, width):
+        super().__init__(batch, spec, width)
+        self.width = spec.num_ceps
+        _native.stages4_lib()  # (a missing or stale library is an error here, not in the first tick)
+
+    def plan(self, up, ids, rows, final):
+        return rows
+
+    def launch(self, up, rows, ids, stream):
+        return self.spec.apply_rows(rows)  # one launch on `stream`, none without rows
+
+
 class _CmvnStage(_Stage):
     """`cmvn`: `spec` is :func:`streaming_cmvn`'s ``(Standardize, prior, norm_var)`` and whether the statistics run.
     Pools: ``sums``, float64 ``(capacity, 2, F)`` (running statistics only; a fresh stream's slot is never read: no
@@ -1146,7 +1187,7 @@ class _TickBatch:
     _launch_extra = ()
 
     def __init__(self, computer, capacity: int = 4096, dtype=np.float32, deltas=None, preemphasis=None, cmvn=None,
-                 cmvn_running=True, stack=None, dither=None, cepstra=None, sliding_cmvn=None, pcen=None):
+                 cmvn_running=True, stack=None, dither=None, cepstra=None, sliding_cmvn=None, pcen=None, plp=None):
         # every argument is read before a device is touched
         if not isinstance(computer, self._computer_type):
             raise TypeError(self._wrong_computer)
@@ -1158,10 +1199,17 @@ class _TickBatch:
         # the width the cmvn sees is the cepstral one with `cepstra` (whose bounds on the computer's width are checked
         # here, where it is known)
         pspec = streaming_cepstra(cepstra)
+        if plp is not None and (pspec is not None or espec is not None):
+            raise ValueError("StreamBatch: plp stands in cepstra's place and takes the linear energies themselves: "
+                             "give it without cepstra and pcen")
+        # ... and PLP's (its centre frequencies and its energy column are the computer's where it leaves them open)
+        lspec = streaming_plp(plp, computer)
         width = computer.num_coeffs
         if pspec is not None:
             pspec._split(width)
             width = pspec.num_ceps
+        if lspec is not None:
+            width = lspec.num_ceps
         cspec = streaming_cmvn(cmvn, bool(cmvn_running), width)
         wspec = streaming_sliding_cmvn(sliding_cmvn)
         if cspec is not None and wspec is not None:
@@ -1210,7 +1258,7 @@ class _TickBatch:
         if cspec is not None:
             cspec += (bool(cmvn_running),)
         for name, kind, spec in (("pcen", _PcenStage, espec), ("cepstra", _CepstraStage, pspec),
-                                 ("cmvn", _CmvnStage, cspec),
+                                 ("plp", _PlpStage, lspec), ("cmvn", _CmvnStage, cspec),
                                  ("sliding", _SlidingStage, wspec), ("deltas", _DeltasStage, dspec),
                                  ("stack", _StackStage, kspec)):
             if spec is not None:
@@ -1589,6 +1637,14 @@ class StreamBatch(_TickBatch):
     :attr:`lookahead` do not change; ``finalize`` returns a stream to fresh; :func:`pcen_smooth` reads a stream's
     current M.  Additional device memory: ``capacity * F`` float64.  A tick's upload grows by two words and one byte
     per stream.
+
+    `plp`: a :class:`post.PLP` (or what ``alias_factory_subclass_from_arg(PostProcessor, ...)`` makes one: ``"plp"``,
+    ``{"name": "plp", "num_ceps": 13}``); ``None``: none.  It stands in `cepstra`'s place -- giving it together with
+    `cepstra` or `pcen` is a ``ValueError`` -- and every static row becomes its `num_ceps` PLP cepstra, which `cmvn` /
+    `sliding_cmvn`, `deltas` and `stack` work on: a stream's rows are ``stack(deltas(cmvn(plp.apply(statics))))`` of the
+    offline objects over its whole utterance, bit for bit.  The object's centre frequencies and `energy` are taken from
+    `computer` where it leaves them open; a computer built with ``use_log=True`` and a width the object refuses are
+    ``ValueError`` s.  No additional device memory, no additional upload.
 
     `dither`: a :class:`pre.Dither` (or what ``alias_factory_subclass_from_arg(PreProcessor, ...)`` makes one:
     ``"dither"``, ``{"name": "dither", "coeff": 1.0, "seed": 5}``); ``None`` or a coefficient of 0: none.  Every

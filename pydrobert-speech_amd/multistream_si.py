@@ -186,7 +186,8 @@ class SiStreamBatch(_TickBatch):
     state is not touched).  `capacity`, `dtype`, `deltas`, `preemphasis`, `cmvn`, `cmvn_running`, `stack`, `dither`, `cepstra`,
     `sliding_cmvn` (sliding-window CMVN in the place of `cmvn`; its ring of ``cmn_window + 1`` rows per stream is added
     to the device memory below), `pcen` (per-channel energy normalisation as the first post stage, for a computer with
-    ``use_log=False``; ``capacity * F`` float64 more) and every method (``cmvn_stats`` and ``dither_seeds`` among them): as :class:`multistream.StreamBatch` -- with `dither`
+    ``use_log=False``; ``capacity * F`` float64 more), `plp` (PLP cepstra in `cepstra`'s place, for a computer with
+    ``use_log=False``; no device memory of its own) and every method (``cmvn_stats`` and ``dither_seeds`` among them): as :class:`multistream.StreamBatch` -- with `dither`
     every stream's raw signal is dithered across ticks, before the pre-emphasis; with `cmvn` the static rows are
     standardised frame by frame, running or by fixed statistics, before the deltas are taken, and with `stack` the rows
     are stacked last.  Device memory: the carry pool, ``2 * capacity * row_length`` samples with

@@ -1,5 +1,5 @@
 """Post-processors on the hot path: ``Deltas``, ``Standardize`` / ``CMVN``, ``Cepstra``, ``SlidingCMVN``, ``EnergyVAD``,
-``PCEN``, ``SpecAugment``.
+``PCEN``, ``SpecAugment``, ``PLP``.
 
 Same classes, aliases, arguments and error behaviour as the reference's (post.py:38-491);
 the element-wise and stencil arithmetic runs in HIP kernels (``csrc/post.hip``) -- there
@@ -24,11 +24,15 @@ packed ragged batch.
 for training, drawn from a counter-based generator keyed per utterance, three HIP kernels of the third stages library
 (``csrc/specaug.hip``) over a packed ragged batch.
 
+``PLP`` is not in the reference either: perceptual linear prediction cepstra of linear filter-bank energies, Kaldi's
+third feature type, row by row in one HIP kernel of the fourth stages library (``csrc/plp.hip``).
+
 ``Stack`` moves data only: views for a single tensor, one copy
 kernel for a packed ragged batch.  CMVN statistics files (``rfilename``, ``save``) go through
 ``util.read_signal`` / numpy.
 """
 import abc
+import math
 import warnings
 from typing import Callable, Optional, Tuple, Union
 
@@ -38,8 +42,8 @@ from . import _native
 from . import pre as _pre
 from .alias import AliasedFactory
 
-__all__ = ["CMVN", "Cepstra", "Deltas", "EnergyVAD", "PCEN", "PostProcessor", "SlidingCMVN", "SpecAugment", "Stack",
-           "Standardize"]
+__all__ = ["CMVN", "Cepstra", "Deltas", "EnergyVAD", "PCEN", "PLP", "PostProcessor", "SlidingCMVN", "SpecAugment",
+           "Stack", "Standardize"]
 
 
 class PostProcessor(AliasedFactory):
@@ -1200,11 +1204,11 @@ def _pcen_number(value, what):
     return value
 
 
-def refuse_log_computer(computer) -> None:
+def refuse_log_computer(computer, who: str = "PCEN") -> None:
     """``ValueError`` if `computer` (an STFT or short-integration frame computer) takes the logarithm of its
-    energies (its ``use_log``): PCEN takes linear energies"""
+    energies (its ``use_log``): PCEN -- and PLP, `who` -- takes linear energies"""
     if bool(getattr(computer, "_log", False)):
-        raise ValueError("PCEN takes linear energies: the computer takes their logarithm (build it with use_log=False)")
+        raise ValueError(f"{who} takes linear energies: the computer takes their logarithm (build it with use_log=False)")
 
 
 class PCEN(PostProcessor):
@@ -1408,6 +1412,330 @@ def _finish_rows(out, lead, axis, on_gpu, features, in_place):
         features[...] = res
         return features
     return res
+
+
+# ------------------------------------------------------------------ PLP --------------
+
+_PLP_MAX_WIDTH = 256  # columns of an input row pds_plp_rows serves (include/pds_amd_stages4.h)
+_PLP_MAX_ORDER = 32  # ... and the largest LPC order
+_PLP_BLOCK_ROWS = 64  # rows of a block of it (pds_plp_block_rows, csrc/plp_rule.h)
+_PLP_MAX_BLOCKS = (1 << 31) - 1  # ... and the blocks one call of it may launch
+
+
+def _plp_int(value, what, lo, hi):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not lo <= value <= hi:
+        raise ValueError(f"PLP: {what} must be an integer in [{lo}, {hi}], got {value!r}")
+    return int(value)
+
+
+def _plp_number(value, what):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"PLP: {what} must be a number, got {value!r}")
+    return float(value)
+
+
+def _plp_lifter(value, what):
+    # (as Cepstra checks its lifter: a number, finite, not negative)
+    value = _plp_number(value, what)
+    if not np.isfinite(value) or value < 0:
+        raise ValueError(f"PLP: {what} must be finite and not negative, got {value!r}")
+    return value
+
+
+class PLP(PostProcessor):
+    """Perceptual linear prediction (PLP) cepstra of linear filter-bank energies, modelled on Kaldi's
+    ``feature-plp.cc``: an equal-loudness weighting, a root compression, an inverse DFT to autocorrelations, the
+    Levinson-Durbin recursion and the LPC-to-cepstrum recursion, row by row, in one HIP kernel of the fourth stages
+    library (``csrc/plp.hip``)
+
+    `axis` of :func:`apply` is the *coefficient* axis, of width W; it becomes `num_ceps` wide, every other axis is
+    kept.  The input is the linear energies of a computer built with ``use_log=False`` (``use_power=True`` gives
+    Kaldi's PLP).  float32 and float64 keep their dtype; anything else is computed and returned as float64.
+
+    The definition.
+
+    Notation for a row `x` of width `W`:
+
+    - `copy = int(energy)`
+    - `F = W − copy ≥ 1`
+    - `D = F + 2`
+    - `p = lpc_order`
+    - `K = num_ceps`
+
+    Refused with `ValueError`, before any device work:
+
+    - `W > 256`
+    - `p` outside `[1, min(F + 1, 32)]`
+    - `K` outside `[1, p + 1]`
+    - `compress_factor` not finite or not positive
+    - `floor` not positive
+    - `lifter` or `scale` as `Cepstra` checks its `lifter`
+    - `equal_loudness=True` without `F` centre frequencies
+
+    Host tables, float64, built once per `(width, device)`:
+
+    - `w[f]`, the equal-loudness weight.
+      - It is `1.0` when `equal_loudness=False`.
+      - Otherwise `fsq = c_f²`, `fs = fsq / (fsq + 1.6e5)` and `w[f] = fs · fs · ((fsq + 1.44e6) / (fsq + 9.61e6))` for
+        centre `c_f` in Hz.
+    - `B[i][j]` for `0 ≤ i ≤ p`, `0 ≤ j < D`, with `s = 1 / (2 (D − 1))` and `θ = π / (D − 1)`:
+      - `B[i][0] = s`
+      - `B[i][j] = 2 s cos(θ i j)` for `0 < j < D − 1`
+      - `B[i][D−1] = s cos(θ i (D − 1))`
+    - `L[k] = scale · (1 + 0.5 Q sin(π k / Q))` with `Q = lifter`, for `0 ≤ k < K`.
+      - `lifter` of `0` or `None` means no lifter: `L[k] = scale`.
+
+    Per row, float64 throughout. Every operation is rounded by itself (no contraction: `-ffp-contract=off` for the
+    object).
+
+    1. Widen the row exactly: `e[f] = float64(x[copy + f])`.
+    2. Floor: `g[f] = (e[f] < floor) ? floor : e[f]`. A NaN passes.
+    3. Compress: `h[f] = pow(g[f] · w[f], compress_factor)`. The product is rounded once, then the device's `pow`.
+    4. Duplicate the edges: `d[0] = h[0]`, `d[1 + f] = h[f]`, `d[D − 1] = h[F − 1]`.
+    5. Autocorrelation: `r[i]` starts at `+0.0` and takes `r[i] = r[i] + B[i][j] · d[j]` for `j = 0 … D − 1`, in that
+       order.
+    6. Durbin. `E = r[0]`. For `i = 0 … p − 1`:
+       1. `k = r[i+1]`, then `k = k + a[j] · r[i − j]` for `j = 0 … i − 1`.
+       2. `k = k / E`.
+       3. `c = 1 − k · k`, then `c = (c < 1e-5) ? 1e-5 : c`.
+       4. `E = E · c`.
+       5. `t[i] = −k`, and `t[j] = a[j] − k · a[i − j − 1]` for `j < i`.
+       6. `a[0..i] = t[0..i]`.
+    7. Cepstrum. For `i = 0 … p − 1`:
+       1. `s = +0.0`.
+       2. `s = s + (double(i − j) · a[j]) · q[i − j − 1]` for `j = 0 … i − 1`.
+       3. `q[i] = −a[i] − s / double(i + 1)`.
+    8. Output, each value rounded once to the row's dtype.
+       - Without `energy`: `out[0] = L[0] · log(E)`, using the device's `log`.
+       - With `energy`: `out[0] = log((e0 < floor) ? floor : e0)`, where `e0` is the widened column 0. It is neither
+         lifted nor scaled.
+       - `out[k] = L[k] · q[k − 1]` for `1 ≤ k < K`.
+       - The output width is `K`.
+
+    Consequences:
+
+    - Everything but the `pow` of step 3 and the `log` of step 8 is plain IEEE arithmetic, so numpy reproduces it bit
+      for bit **given the same `d`**.
+    - A row holding a NaN gives NaN in every computed column, and the clamp in step 6 is written so that it does.
+    - A row holding +inf is only promised not to disturb other rows.
+    - A row of zeros is finite, because of the floor.
+
+    `centers_hz`: the filters' centre frequencies, ``bank.centers_hz`` of the computer; :func:`for_computer`,
+    ``StreamBatch(plp=...)`` and the command-line tool take them from their computer when the object has none.
+    `energy`: column 0 is the energy of a computer built with ``include_energy=True``; ``None``, the default, reads as
+    ``False`` and lets those three take it from their computer too (:attr:`energy` is always a bool).
+
+    :func:`apply`, :func:`apply_rows` and the streaming stage launch the same kernel, whose every instantiation inlines
+    one row function (``csrc/plp_rule.h``): their results agree bit for bit.  :func:`apply_rows` takes an `aux` buffer
+    for the row's `d` and final `E`, which is what makes the claim above checkable.
+    """
+
+    aliases = {"plp", "plp_cepstra", "rasta_plp_off"}
+
+    def __init__(self, num_ceps: int = 13, lpc_order: int = 12, compress_factor: float = 1.0 / 3.0,
+                 lifter: Optional[float] = 22.0, scale: float = 1.0, equal_loudness: bool = True, centers_hz=None,
+                 floor: float = 2.0 ** -126, energy: Optional[bool] = None):
+        self.lpc_order = _plp_int(lpc_order, "lpc_order", 1, _PLP_MAX_ORDER)
+        self.num_ceps = _plp_int(num_ceps, "num_ceps", 1, self.lpc_order + 1)
+        self.compress_factor = _plp_number(compress_factor, "compress_factor")
+        if not np.isfinite(self.compress_factor) or not self.compress_factor > 0.0:
+            raise ValueError(f"PLP: compress_factor must be finite and positive, got {compress_factor!r}")
+        self.floor = _plp_number(floor, "floor")
+        if not self.floor > 0.0 or not np.isfinite(self.floor):
+            raise ValueError(f"PLP: floor must be positive and finite, got {floor!r}")
+        self.lifter = _plp_lifter(0.0 if lifter is None else lifter, "lifter")
+        self.scale = _plp_lifter(scale, "scale")
+        if not isinstance(equal_loudness, (bool, np.bool_)):
+            raise ValueError(f"PLP: equal_loudness must be a bool, got {equal_loudness!r}")
+        self.equal_loudness = bool(equal_loudness)
+        if energy is not None and not isinstance(energy, (bool, np.bool_)):
+            raise ValueError(f"PLP: energy must be a bool or None, got {energy!r}")
+        self._energy_given = energy is not None
+        self.energy = bool(energy)
+        if centers_hz is not None:
+            try:
+                centers = np.asarray(centers_hz, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"PLP: centers_hz must be a sequence of frequencies in Hz, got {centers_hz!r}")
+            if centers.ndim != 1 or not len(centers) or not np.isfinite(centers).all() or (centers < 0).any():
+                raise ValueError("PLP: centers_hz must be a non-empty sequence of finite frequencies in Hz, none negative")
+            centers_hz = tuple(float(c) for c in centers)
+        self.centers_hz = centers_hz
+        self._device_tables = {}  # (width, device) -> device float64 w[F], B[p + 1, D], L[K]
+
+    # ---- what a computer knows ------------------------------------------------------
+
+    def _arguments(self) -> dict:
+        return dict(num_ceps=self.num_ceps, lpc_order=self.lpc_order, compress_factor=self.compress_factor,
+                    lifter=self.lifter, scale=self.scale, equal_loudness=self.equal_loudness,
+                    centers_hz=self.centers_hz, floor=self.floor, energy=self.energy if self._energy_given else None)
+
+    def bound_to(self, computer) -> "PLP":
+        """This object with what it leaves open taken from `computer` (a frame computer over a filter bank): the centre
+        frequencies from ``computer.bank.centers_hz`` if it has none and weights by them, `energy` from
+        ``computer.includes_energy`` if it was not given.  The object itself if nothing was open; it is not changed.
+        ``ValueError`` for a computer that takes logs"""
+        refuse_log_computer(computer, "PLP")
+        args = self._arguments()
+        if args["energy"] is None:
+            args["energy"] = bool(getattr(computer, "includes_energy", False))
+        if args["centers_hz"] is None and self.equal_loudness:
+            args["centers_hz"] = tuple(float(c) for c in computer.bank.centers_hz)
+        if args["centers_hz"] == self.centers_hz and self._energy_given:
+            return self
+        return PLP(**args)
+
+    @classmethod
+    def for_computer(cls, computer, **kw) -> "PLP":
+        """``PLP(**kw)`` for the rows of `computer`: `centers_hz` from ``computer.bank.centers_hz`` and `energy` from
+        ``computer.includes_energy`` unless given; ``ValueError`` for a computer that takes logs"""
+        return cls(**kw).bound_to(computer)
+
+    # ---- the host tables ------------------------------------------------------------
+
+    def aux_width(self, width: int) -> int:
+        """columns of :func:`apply_rows`' `aux` for input rows of `width` columns: ``D + 1 = F + 3``"""
+        return int(width) - int(self.energy) + 3
+
+    def _split(self, width: int) -> Tuple[int, int]:
+        """``(F, copy)`` of input rows of `width` columns, or ``ValueError``: the width is only known at apply"""
+        width, copy = int(width), int(self.energy)
+        F = width - copy
+        if width > _PLP_MAX_WIDTH:
+            raise ValueError(f"PLP: rows of {width} coefficients; at most {_PLP_MAX_WIDTH} are served")
+        if F < 1:
+            raise ValueError(f"PLP: rows of {width} coefficients{' (the energy among them)' if copy else ''} hold no "
+                             "filter-bank energy")
+        if self.lpc_order > F + 1:
+            raise ValueError(f"PLP: lpc_order = {self.lpc_order} needs at least {self.lpc_order - 1} filter-bank "
+                             f"energies, got {F}")
+        if self.equal_loudness and (self.centers_hz is None or len(self.centers_hz) != F):
+            have = "none" if self.centers_hz is None else str(len(self.centers_hz))
+            raise ValueError(f"PLP: equal_loudness needs the {F} centre frequencies of the filters (centers_hz), got "
+                             f"{have}: PLP.for_computer(computer) takes them from the bank")
+        return F, copy
+
+    def tables(self, width: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The float64 host tables ``(w[F], B[p + 1, D], L[K])`` of the definition for rows of `width` columns"""
+        F, _ = self._split(width)
+        D, p = F + 2, self.lpc_order
+        if self.equal_loudness:
+            c = np.asarray(self.centers_hz, dtype=np.float64)
+            fsq = c * c
+            fs = fsq / (fsq + 1.6e5)
+            w = fs * fs * ((fsq + 1.44e6) / (fsq + 9.61e6))
+        else:
+            w = np.ones(F, dtype=np.float64)
+        s = 1.0 / (2 * (D - 1))
+        theta = math.pi / (D - 1)
+        # (the C library's cos and sin, one call an element: an array call may take another code path with other
+        # roundings, and the tables are part of the definition)
+        B = np.empty((p + 1, D), dtype=np.float64)
+        for i in range(p + 1):
+            B[i, 0] = s
+            for j in range(1, D - 1):
+                B[i, j] = 2.0 * s * math.cos(theta * i * j)
+            B[i, D - 1] = s * math.cos(theta * i * (D - 1))
+        L = np.full(self.num_ceps, self.scale, dtype=np.float64)
+        if self.lifter:
+            for k in range(self.num_ceps):
+                L[k] = self.scale * (1.0 + 0.5 * self.lifter * math.sin(math.pi * k / self.lifter))
+        return np.ascontiguousarray(w), np.ascontiguousarray(B), np.ascontiguousarray(L)
+
+    def _tables_on(self, width, device):
+        key = (int(width), str(device))
+        if key not in self._device_tables:
+            tables = self.tables(width)
+            torch = _native.require_device()
+            self._device_tables[key] = tuple(torch.from_numpy(t).to(device) for t in tables)
+        return self._device_tables[key]
+
+    # ---- packed rows ----------------------------------------------------------------
+
+    def apply_rows(self, feats, row_offsets=None, out=None, aux=None):
+        """The rows of a packed batch, each by itself, in one launch on the GPU
+
+        `feats`: ``(total_rows, W)`` float32 or float64 GPU tensor (rows may be strided: a column slice of a wider
+        tensor).  `row_offsets`: the utterances' ``B + 1`` ascending row indices, of which only the first and the last
+        matter here -- a row depends on nothing but itself --, or ``None`` for every row.  Returns ``(total_rows,
+        num_ceps)`` of `feats`' dtype (`out`, if given: its rows contiguous, possibly strided, not overlapping `feats`);
+        rows outside ``row_offsets[0]:row_offsets[-1]`` and columns past `num_ceps` of a wider `out` are not written.
+        `aux`: ``None`` or a contiguous float64 GPU tensor ``(total_rows, aux_width(W))`` that takes the row's
+        ``d[0 .. D - 1]`` and its final ``E``.
+        """
+        F, copy = self._split(feats.shape[1]) if getattr(feats, "ndim", 0) == 2 else (0, 0)
+        torch = _native.require_device()
+        lib = _native.stages4_lib()
+        if not _is_gpu_tensor(feats) or feats.dtype not in (torch.float32, torch.float64) or feats.dim() != 2:
+            raise ValueError("feats must be a 2-D float32 or float64 GPU tensor")
+        if feats.stride(1) != 1:
+            feats = feats.contiguous()
+        R, W = feats.shape
+        K = self.num_ceps
+        stride = feats.stride(0) if R > 1 else W
+        if stride < W:
+            raise ValueError("rows of feats must not overlap")
+        first, last = 0, R
+        if row_offsets is not None:
+            rows = np.ascontiguousarray(row_offsets, dtype=np.int64)
+            if rows.ndim != 1 or len(rows) < 1 or (np.diff(rows) < 0).any() or rows[0] < 0 or rows[-1] > R:
+                raise ValueError("row_offsets must be B + 1 ascending row indices within feats")
+            first, last = int(rows[0]), int(rows[-1])
+        if out is None:
+            out = torch.empty((R, K), dtype=feats.dtype, device=feats.device)
+        elif (not _is_gpu_tensor(out) or out.dtype != feats.dtype or out.device != feats.device
+              or tuple(out.shape) != (R, K) or out.stride(1) != 1):
+            raise ValueError("out must be a GPU tensor of (rows of feats, num_ceps), feats' dtype and device, with "
+                             "contiguous rows")
+        out_stride = out.stride(0) if R > 1 else K
+        if out_stride < K:
+            raise ValueError("rows of out must not overlap")
+        if R and out.untyped_storage().data_ptr() == feats.untyped_storage().data_ptr():
+            raise ValueError("out must not share feats' memory: the shape changes, nothing is done in place")
+        if aux is not None and (not _is_gpu_tensor(aux) or aux.dtype != torch.float64 or aux.device != feats.device
+                                or tuple(aux.shape) != (R, F + 3) or not aux.is_contiguous()):
+            raise ValueError(f"aux must be a contiguous float64 GPU tensor of shape ({R}, {F + 3}) on feats' device")
+        if last == first:
+            return out
+        d_w, d_B, d_L = self._tables_on(W, feats.device)
+        fn = lib.pds_plp_rows_f32 if feats.dtype == torch.float32 else lib.pds_plp_rows_f64
+        step = _PLP_BLOCK_ROWS * _PLP_MAX_BLOCKS  # one launch, unless there are more rows than a grid has blocks for
+        with torch.cuda.device(feats.device):
+            for lo in range(first, last, step):
+                n = min(last, lo + step) - lo
+                rc = fn(feats[lo:].data_ptr(), stride, n, F, copy, d_w.data_ptr(), d_B.data_ptr(), d_L.data_ptr(),
+                        self.lpc_order, K, self.compress_factor, self.floor, out[lo:].data_ptr(), out_stride,
+                        aux[lo:].data_ptr() if aux is not None else None, _stream(torch, feats))
+                _native.check_stages4(rc, "pds_plp_rows")
+        return out
+
+    # ---- arrays and tensors ---------------------------------------------------------
+
+    def apply(self, features, axis: int = -1, in_place: bool = False):
+        # (`in_place` is accepted and ignored: the shape changes)
+        on_gpu = _is_gpu_tensor(features)
+        if not on_gpu:
+            features = np.asarray(features)
+        shape = tuple(features.shape)
+        if not shape:
+            raise ValueError("PLP: expected at least one dimension")
+        axis = axis % len(shape)
+        W = shape[axis]
+        self._split(W)  # (the width's errors come before any device work)
+        torch = _native.require_device()
+        if on_gpu:
+            t = features if features.dtype in (torch.float32, torch.float64) else features.to(torch.float64)
+        else:
+            t = _to_device(features if features.dtype in (np.float32, np.float64) else features.astype(np.float64))
+        rows = t.movedim(axis, -1)
+        lead = tuple(rows.shape[:-1])
+        # a matrix whose rows are contiguous goes as it is, whatever its row stride (a column slice of a wider
+        # tensor); anything else as a contiguous (rows, W) copy
+        if not (rows.dim() == 2 and rows.stride(1) == 1 and (rows.stride(0) >= W or rows.shape[0] <= 1)):
+            rows = rows.reshape(int(np.prod(lead, dtype=np.int64)), W).contiguous()
+        out = self.apply_rows(rows)
+        out = out.reshape(lead + (self.num_ceps,)).movedim(-1, axis)
+        return out if on_gpu else out.cpu().numpy()
 
 
 # ------------------------------------------------------------------ SpecAugment ------

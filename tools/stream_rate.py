@@ -3,7 +3,7 @@
 
     python tools/stream_rate.py [--streams 64,1024,8192] [--ticks 200] [--loop 64,256] [--deltas] [--cmvn]
                                 [--stack N] [--dither] [--cepstra N] [--sliding W] [--samples {f32,i16}] [--preemph C]
-                                [--si] [--pcen]
+                                [--si] [--pcen] [--plp]
                                 > profiles/<tag>_stream_rate.txt
 
 Configuration c1_readme_fbank of tests/golden/configs.json (16 kHz, 25 ms frames, 10 ms shift), 160-sample (10 ms)
@@ -30,7 +30,10 @@ StreamBatch(sliding_cmvn=SlidingCMVN(W, 1)), every static row normalised over th
 the timed ones work on full windows, rebuilt every W frames), and no loop.  --pcen: the computer is built with
 use_log=False for the whole run, and the same ticks go once more through StreamBatch(pcen=PCEN()), every static row
 normalised by its stream's smoother and compressed (rows "host+e" / "packed+e": one more launch per tick, two words
-and a byte more per stream in the upload, the same download), and no loop.  --samples i16: the chunks are 16-bit PCM, int16 arrays on the host (two bytes per sample over
+and a byte more per stream in the upload, the same download), and no loop.  --plp: the computer is built with
+use_log=False for the whole run too, and the same ticks go once more through StreamBatch(plp=PLP()), every static row
+turned into its 13 PLP cepstra (rows "host+l" / "packed+l": one more launch per tick, no more upload, a download of 13
+columns instead of the computer's), and no loop.  --samples i16: the chunks are 16-bit PCM, int16 arrays on the host (two bytes per sample over
 the link) and an int16 tensor on the GPU; --preemph C: StreamBatch(preemphasis=C), the pre-emphasis carried across
 ticks in the assemble launch.  Either leaves the loop out (a single-stream compute_chunk has no counterpart to them).
 
@@ -73,6 +76,8 @@ def main():
                     help="also time the ticks with sliding_cmvn=SlidingCMVN(W, 1); skips the loop")
     ap.add_argument("--pcen", action="store_true",
                     help="linear energies (use_log=False) and also the ticks with pcen=PCEN(); skips the loop")
+    ap.add_argument("--plp", action="store_true",
+                    help="linear energies (use_log=False) and also the ticks with plp=PLP(); skips the loop")
     ap.add_argument("--samples", choices=("f32", "i16"), default="f32", help="sample type of the chunks")
     ap.add_argument("--preemph", type=float, default=0.0, metavar="C", help="pre-emphasis coefficient (0: none)")
     ap.add_argument("--si", action="store_true", help="short-integration streams (SiStreamBatch, s1_gabor_mel)")
@@ -87,15 +92,15 @@ def main():
     from pydrobert_speech_amd.alias import alias_factory_subclass_from_arg
     from pydrobert_speech_amd.multistream import StreamBatch
     from pydrobert_speech_amd.multistream_si import SiStreamBatch
-    from pydrobert_speech_amd.post import PCEN, Cepstra, Deltas, SlidingCMVN, Stack, Standardize
+    from pydrobert_speech_amd.post import PCEN, PLP, Cepstra, Deltas, SlidingCMVN, Stack, Standardize
     from pydrobert_speech_amd.pre import Dither
 
     name = "s1_gabor_mel" if args.si else "c1_readme_fbank"
     Batch = SiStreamBatch if args.si else StreamBatch
     with open(os.path.join(ROOT, "tests", "golden", "si_configs.json" if args.si else "configs.json")) as fh:
         cfg = json.load(fh)["configs"][name]
-    if args.pcen:
-        cfg = dict(cfg, use_log=False)  # (PCEN takes linear energies; the plain ticks of this run do too)
+    if args.pcen or args.plp:
+        cfg = dict(cfg, use_log=False)  # (PCEN and PLP take linear energies; the plain ticks of this run do too)
 
     def computer():
         return alias_factory_subclass_from_arg(ps.compute.FrameComputer, json.loads(json.dumps(cfg)))
@@ -134,6 +139,8 @@ def main():
             apis += ("host+w", "packed+w")
         if args.pcen:
             apis += ("host+e", "packed+e")
+        if args.plp:
+            apis += ("host+l", "packed+l")
         for api in apis:
             stages = api.split(" ")[0].split("+")[1:]
             post = dict(deltas=Deltas(2)) if "d" in stages else dict(cmvn=Standardize()) if "c" in stages else {}
@@ -149,6 +156,8 @@ def main():
                 warm = max(warm, args.sliding + 1)
             if "e" in stages:
                 post["pcen"] = PCEN()
+            if "l" in stages:
+                post["plp"] = PLP()  # (centre frequencies and the energy column: the computer's)
             sb = Batch(comp, capacity=S, **post, **extra)
             times, frames = [], 0
             for t in range(warm + args.ticks):
@@ -175,6 +184,7 @@ def main():
                       f"({min(a, b):.3f} -> {d:.3f}); the plain tick twice in this run: {a:.3f} / {b:.3f}")
     loops = [int(s) for s in args.loop.split(",") if s.strip() and int(s) > 0]  # (--loop 0: none)
     staged = args.deltas or args.cmvn or args.stack > 1 or args.dither or args.cepstra > 0 or args.sliding > 0 or args.pcen
+    staged = staged or args.plp
     for S in [] if staged or variant else loops:
         comps = [computer() for _ in range(S)]
         block = (3000 * rng.standard_normal((S, n))).astype(np.float32)
