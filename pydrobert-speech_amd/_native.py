@@ -1,8 +1,9 @@
 """ctypes binding of ``libpds_amd.so`` (C ABI: ``include/pds_amd.h``), of ``libpds_amd_stages.so``, the stage
 kernels outside the fused kernel's instantiation matrix (C ABI: ``include/pds_amd_stages.h``), of
 ``libpds_amd_stages2.so``, the second capped library of stage kernels (C ABI: ``include/pds_amd_stages2.h``), of
-``libpds_amd_stages3.so``, the third (C ABI: ``include/pds_amd_stages3.h``), and of ``libpds_amd_stages4.so``, the
-fourth (C ABI: ``include/pds_amd_stages4.h``).
+``libpds_amd_stages3.so``, the third (C ABI: ``include/pds_amd_stages3.h``), of ``libpds_amd_stages4.so``, the
+fourth (C ABI: ``include/pds_amd_stages4.h``), and of ``libpds_amd_stages5.so``, the fifth (C ABI:
+``include/pds_amd_stages5.h``).
 
 There is deliberately no fallback: if the shared library is missing or a compute call
 is made without a HIP device, an exception is raised.  Nothing in this package computes
@@ -26,6 +27,9 @@ STAGES3_LIB_PATH = os.environ.get("PDS_AMD_STAGES3_LIB") or os.path.join(os.path
 # ... and PDS_AMD_STAGES4_LIB another build of the fourth stages library; without it the file beside the first library
 STAGES4_LIB_PATH = os.environ.get("PDS_AMD_STAGES4_LIB") or os.path.join(os.path.dirname(LIB_PATH),
                                                                          "libpds_amd_stages4.so")
+# ... and PDS_AMD_STAGES5_LIB another build of the fifth stages library; without it the file beside the first library
+STAGES5_LIB_PATH = os.environ.get("PDS_AMD_STAGES5_LIB") or os.path.join(os.path.dirname(LIB_PATH),
+                                                                         "libpds_amd_stages5.so")
 
 PDS_OK = 0
 
@@ -356,8 +360,36 @@ STAGES4_SIGNATURES = {
     "pds_plp_rows_f64": (c_int32, _PLP_ROWS_ARGS),
 }
 
+_MIX_ENERGY_ARGS = [
+    c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p,  # d_x, d_off, d_len, d_chunk_base, B, total_chunks, d_partials, stream
+]
+_MIX_APPLY_ARGS = [
+    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,  # d_x, d_off, d_len, d_bank, d_clip_off, d_clip_len, d_start
+    c_void_p, c_int32, c_int64, c_void_p, c_void_p,  # d_gain, B, max_len, d_out, stream
+]
+
+# name -> (restype, argtypes); every symbol include/pds_amd_stages5.h declares
+STAGES5_SIGNATURES = {
+    "pds_stages5_version": (c_int32, []),
+    "pds_stages5_last_error": (c_char_p, []),
+    "pds_mix_chunk_samples": (c_int64, []),
+    "pds_mix_chunk_count": (c_int64, [c_int64]),
+    "pds_mix_tile_samples": (c_int64, []),
+    "pds_mix_chunk_energy_f32": (c_int32, _MIX_ENERGY_ARGS),
+    "pds_mix_chunk_energy_f64": (c_int32, _MIX_ENERGY_ARGS),
+    "pds_mix_chunk_energy_i16": (c_int32, _MIX_ENERGY_ARGS),
+    "pds_mix_gain": (
+        c_int32,
+        [c_void_p, c_void_p, c_void_p, c_int32, c_int32,  # d_partials, d_chunk_base, d_len, B, mode
+         c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p],  # d_clip, d_ratio, d_applied, d_pn, K, d_out, stream
+    ),
+}
+STAGES5_SIGNATURES.update({f"pds_mix_apply_{x}_{z}": (c_int32, _MIX_APPLY_ARGS)
+                           for x in ("f32", "f64", "i16") for z in ("f32", "f64", "i16")})
+
 _lib = None
 _stages_lib = None
+_stages5_lib = None
 _stages2_lib = None
 _stages3_lib = None
 _stages4_lib = None
@@ -476,6 +508,28 @@ def stages4_lib() -> ctypes.CDLL:
     return _stages4_lib
 
 
+def stages5_lib() -> ctypes.CDLL:
+    """The loaded fifth stages library; raises :class:`NativeError` if it has not been built"""
+    global _stages5_lib
+    if _stages5_lib is None:
+        if not os.path.exists(STAGES5_LIB_PATH):
+            raise NativeError(
+                f"{STAGES5_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
+                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
+            )
+        try:  # (torch's HIP runtime first, as for lib())
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        loaded = ctypes.CDLL(STAGES5_LIB_PATH)
+        for name, (restype, argtypes) in STAGES5_SIGNATURES.items():
+            fn = getattr(loaded, name)  # AttributeError if the .so is stale
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _stages5_lib = loaded
+    return _stages5_lib
+
+
 def last_error() -> str:
     return lib().pds_last_error().decode("utf-8", "replace")
 
@@ -521,6 +575,15 @@ def check_stages4(rc: int, what: str) -> None:
     """:func:`check` for a call into the fourth stages library, which keeps its own error string"""
     if rc != PDS_OK:
         msg = stages4_lib().pds_stages4_last_error().decode("utf-8", "replace")
+        if rc == -1:
+            raise ValueError(f"{what}: {msg}")
+        raise NativeError(f"{what}: {msg} (code {rc})")
+
+
+def check_stages5(rc: int, what: str) -> None:
+    """:func:`check` for a call into the fifth stages library, which keeps its own error string"""
+    if rc != PDS_OK:
+        msg = stages5_lib().pds_stages5_last_error().decode("utf-8", "replace")
         if rc == -1:
             raise ValueError(f"{what}: {msg}")
         raise NativeError(f"{what}: {msg} (code {rc})")

@@ -15,7 +15,13 @@ Same command line and on-disk result as the reference's tool -- a text map of
   up than they save (tools/driver_rate.py: 0.6-0.9 s without, 1.4-2.1 s with);
 * a batch of utterances (``--batch-utts`` / ``--batch-samples``) is packed into one device
   buffer and goes through ONE launch per stage: rate conversion (``--preprocess '[{"name": "resample",
-  "from_rate": 8000, "to_rate": 16000}, "preemphasis"]'``: the stages behind it see the resampled batch), dither,
+  "from_rate": 8000, "to_rate": 16000}, "preemphasis"]'``: the stages behind it see the resampled batch), noise
+  mixing (``{"name": "add_noise", "clips": ["n1.wav", "n2.npy"], "snr_db": [0, 15]}``, at any place in the list: a clip
+  of the bank is added to every utterance at a signal-to-noise ratio drawn per utterance, ``AddNoise.apply_packed``;
+  the clips are taken to be at the rate of the signal where the stage stands, so it goes behind a ``resample``; with
+  ``--seed`` it is seeded per utterance with ``seed + index`` like the dither, so the files do not depend on how the
+  corpus was batched and ``--seed 1``, ``--seed 2``, ... give one noisy copy each; without ``--seed`` the object's own
+  seed sequence is used), dither,
   pre-emphasis (fused into the frame loader when it is the last pre-processor), the fused STFT/filter-bank kernel, then each
   post-processor over the packed rows (a ``Cepstra`` -- ``--postprocess '[{"name": "mfcc", "num_ceps": 13}]'`` --
   works row by row, so the whole batch is one call and one launch, and the row offsets stay as they are; a
@@ -58,7 +64,7 @@ from .alias import alias_factory_subclass_from_arg
 from .compute import FrameComputer
 from .post import (PCEN, PLP, Cepstra, Deltas, EnergyVAD, PostProcessor, SlidingCMVN, SpecAugment, Stack, Standardize,
                    refuse_log_computer)
-from .pre import Dither, Preemphasize, PreProcessor, Resample
+from .pre import AddNoise, Dither, Preemphasize, PreProcessor, Resample
 from .util import SIGNAL_SOURCES, read_signal
 
 __all__ = ["FeatureDirWriter", "signals_to_torch_feat_dir"]
@@ -101,7 +107,8 @@ def _parse(args):
                     help="JSON list of PostProcessor configurations, applied in order")
     ap.add_argument("--force-as", default=None, choices=sorted(SIGNAL_SOURCES),
                     help="read every path as this type instead of going by its name")
-    ap.add_argument("--seed", type=_nonneg, default=None, help="seed for dithering")
+    ap.add_argument("--seed", type=_nonneg, default=None,
+                    help="seed for dithering, noise mixing (add_noise) and SpecAugment: utterance i gets seed + i")
     ap.add_argument("--file-prefix", default="")
     ap.add_argument("--file-suffix", default=".pt")
     ap.add_argument("--num-workers", type=_nonneg, default=0,
@@ -128,9 +135,10 @@ class FeatureDirWriter:
     def __init__(self, computer: Optional[FrameComputer], preprocessors: Sequence[PreProcessor],
                  postprocessors: Sequence[PostProcessor], out_dir: str, channel: int = -1,
                  force_as: Optional[str] = None, seed: int = 0, file_prefix: str = "",
-                 file_suffix: str = ".pt", manifest=None, precision: str = "float32", staging_ring: bool = False):
+                 file_suffix: str = ".pt", manifest=None, precision: str = "float32", staging_ring: bool = False,
+                 seeded: bool = True):
         for pre in preprocessors:
-            if not isinstance(pre, (Dither, Preemphasize, Resample)):
+            if not isinstance(pre, (AddNoise, Dither, Preemphasize, Resample)):
                 raise NotImplementedError(f"pre-processor {type(pre).__name__}")
         if computer is not None and any(isinstance(post, PCEN) for post in postprocessors):
             refuse_log_computer(computer)  # (PCEN takes linear energies)
@@ -144,6 +152,7 @@ class FeatureDirWriter:
         self.prefix, self.suffix, self.manifest = file_prefix, file_suffix, manifest
         self.dtype = np.dtype(precision)
         self.staging_ring = bool(staging_ring)
+        self.seeded = bool(seeded)  # (False: no --seed was given, and an AddNoise draws from its own sequence)
         self._feeds = {}  # sample dtype -> HostFeed
         os.makedirs(out_dir, exist_ok=True)
 
@@ -185,7 +194,7 @@ class FeatureDirWriter:
             return through_feed
         host = np.concatenate(signals) if offsets[-1] else np.zeros(0, self.dtype)
         packed = torch.from_numpy(host).to("cuda")
-        if packed.dtype == torch.int16 and not (self.pre and isinstance(self.pre[0], (Dither, Resample))):
+        if packed.dtype == torch.int16 and not (self.pre and isinstance(self.pre[0], (AddNoise, Dither, Resample))):
             packed = packed.to(torch.float32)  # (uploaded as PCM, widened on the device)
         fused = 0.0
         for k, pre in enumerate(self.pre):
@@ -193,6 +202,11 @@ class FeatureDirWriter:
                 # per-utterance stream, as the reference seeds torch, and one launch for the batch (PCM that is still
                 # int16 is widened by the dither's own load)
                 seeds = [self.seed + first_index + b for b in range(len(signals))]
+                packed = pre.apply_packed(packed, offsets[:-1], lengths, seeds=seeds)
+            elif isinstance(pre, AddNoise):
+                # every utterance under its own key, seed + its index in the run, as the dither: the same file however
+                # it was batched (PCM that is still int16 is widened by the mix's own load)
+                seeds = [self.seed + first_index + b for b in range(len(signals))] if self.seeded else None
                 packed = pre.apply_packed(packed, offsets[:-1], lengths, seeds=seeds)
             elif isinstance(pre, Resample):
                 # the one stage that changes the lengths: the stages behind it get the new offsets and lengths (PCM
@@ -433,7 +447,7 @@ def signals_to_torch_feat_dir(args=None) -> int:
     writer = FeatureDirWriter(
         computer, _as_list(options.preprocess, PreProcessor), _as_list(options.postprocess, PostProcessor),
         options.dir, options.channel, options.force_as, seed, options.file_prefix, options.file_suffix,
-        options.manifest, options.precision, options.staging_ring,
+        options.manifest, options.precision, options.staging_ring, seeded=options.seed is not None,
     )
     writer.run(list(utt2path.items()), options.batch_utts, options.batch_samples, options.num_workers)
     return 0

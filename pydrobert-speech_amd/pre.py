@@ -14,19 +14,24 @@ for one sampling rate: a windowed-sinc rate conversion (Kaldi's ``LinearResample
 exactly, so that one signal (:func:`Resample.apply`), a packed batch in one launch (:func:`Resample.apply_packed`) and
 a stream cut into chunks (``multistream_resample.ResampleBatch``) give the same bits.  It is the one pre-processor that
 changes a signal's length.
+
+``AddNoise`` goes beyond the reference too: the waveform augmentation of Kaldi's multi-condition recipes
+(``wav-reverberate --additive-signals --snrs``), a clip of a noise bank added to every utterance of a packed batch at a
+signal-to-noise ratio drawn per utterance, defined exactly so that a numpy model reproduces it.
 """
 import abc
 import math
 import numbers
+import os
 import warnings
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
 from . import _native
 from .alias import AliasedFactory
 
-__all__ = ["Dither", "PreProcessor", "Preemphasize", "Resample", "dither_keys"]
+__all__ = ["AddNoise", "Dither", "NoisePlan", "PreProcessor", "Preemphasize", "Resample", "dither_keys"]
 
 _AXIS_DEP_MSG = (
     "Specifying axis in preprocessor.apply is deprecated. "
@@ -472,3 +477,446 @@ class Resample(PreProcessor):
                         torch.cuda.current_stream(signal.device).cuda_stream)
                 _native.check_stages(rc, "pds_resample_packed")
         return out, out_offs, out_lens
+
+
+# ---- AddNoise ---------------------------------------------------------------------------------------------------------
+
+_MIX_CHUNK = 16384  # samples of a chunk of the segment energy (csrc/mix_rule.h: MIX_CHUNK)
+_MIX_VEC, _MIX_TILE = 4, 4096  # samples of a lane's group and of a block of the apply kernel (MIX_VEC, MIX_TILE)
+_MIX_ENERGY_WAVES = 4  # chunks of a block of the energy kernel (MIX_ENERGY_WAVES)
+_MIX_MAX_BLOCKS = (1 << 31) - 1  # blocks of one launch (MIX_MAX_BLOCKS)
+_MIX_MAX_UTTS = 65535  # utterances of one launch of the apply kernel (MIX_MAX_UTTS)
+_MIX_COUNTER = (0, 0, 0, 0x4D495831)  # the counter of the plan's Philox block (MIX_COUNTER_0 .. MIX_COUNTER_3)
+_U32 = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def _is_gpu_tensor(x) -> bool:
+    return bool(getattr(x, "is_cuda", False))
+
+
+def _mix_draws(keys: np.ndarray):
+    """x0..x3 of the plan's Philox4x32-10 block under every key of `keys` (uint64): four uint64 arrays of 32-bit
+    values (csrc/mix_rule.h: mix_draw)"""
+    keys = np.asarray(keys, dtype=np.uint64)
+    k0, k1 = keys & _U32, keys >> _S32
+    c = [np.full(keys.shape, word, dtype=np.uint64) for word in _MIX_COUNTER]
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> _S32) ^ c[1] ^ k0, p1 & _U32, (p0 >> _S32) ^ c[3] ^ k1, p0 & _U32]
+        k0 = (k0 + np.uint64(0x9E3779B9)) & _U32
+        k1 = (k1 + np.uint64(0xBB67AE85)) & _U32
+    return c
+
+
+def _mix_pick(x: np.ndarray, n: np.ndarray) -> np.ndarray:
+    """``(x * n) >> 32`` for 32-bit `x` and ``0 <= n < 2^63``, the product taken in two halves (mix_pick)"""
+    n = np.asarray(n, dtype=np.uint64)
+    return ((x * (n >> _S32)) + ((x * (n & _U32)) >> _S32)).astype(np.int64)
+
+
+def _mix_chunks(n):
+    """chunks of segments of `n` samples (an integer or an array)"""
+    n = np.asarray(n, dtype=np.int64)
+    return np.where(n > 0, (n + (_MIX_CHUNK - 1)) // _MIX_CHUNK, 0)
+
+
+class NoisePlan(NamedTuple):
+    """What :func:`AddNoise.plan` draws, one entry per utterance"""
+
+    clip: np.ndarray  #: int64, the clip of the bank
+    start: np.ndarray  #: int64, the first sample read of that clip
+    snr_db: np.ndarray  #: float64, the signal-to-noise ratio in dB
+    ratio: np.ndarray  #: float64, ``10 ** (snr_db / 10)``
+    applied: np.ndarray  #: bool, whether the utterance gets noise at all
+
+
+class AddNoise(PreProcessor):
+    """Add a clip of a noise bank to every utterance at a signal-to-noise ratio drawn per utterance: the additive half
+    of Kaldi's ``wav-reverberate --additive-signals --snrs`` (aliases ``add_noise``, ``additive_noise``, ``mix_noise``)
+
+    `clips` is a non-empty sequence of noise clips, each a 1-D array, a 1-D tensor or a path that the readers of
+    ``util.read_signal`` take (wav, npy, npz, pt); all of one dtype, float32, float64 or int16.  They are packed into
+    one bank, uploaded once per device in that dtype (16-bit PCM stays at two bytes a sample and is widened exactly in
+    the kernel).  `snr_db` is a number or a pair ``(lo, hi)``, ``lo <= hi``; `prob` in ``[0, 1]`` is the share of
+    utterances that get noise at all; `seed` is as ``Dither``'s: an utterance's key comes from :func:`dither_keys`, and
+    with ``seeds=None`` the object's own sequence advances once per utterance.  An utterance's result depends on its
+    key, its samples, the bank and the parameters, not on the batch it stands in, its position there, or the launch.
+
+    The definition.
+
+    Segment energy `E(x, n)` of `n` samples, float64:
+
+    - Chunk `c` covers samples `[c·16384, min(n, (c+1)·16384))`.
+    - In a chunk, lane `l` of 64 starts at `p_l = +0.0`. For `i = l, l+64, …` inside the chunk, in that order, it takes
+      `v = float64(x[i])` and `p_l = p_l + v·v`. The product is rounded by itself, and it is exact for float32 and int16
+      samples.
+    - The chunk sum is the fixed tree: for `s = 32, 16, 8, 4, 2, 1`, `p_l = p_l + p_{l+s}` for all `l < s`. The result
+      is `p_0`.
+    - `E` starts at `+0.0` and takes the chunk sums in ascending order.
+    - `E(x, 0) = 0.0`.
+    - Mean power is `P = E / float64(n)` for `n > 0`, else `0.0`.
+
+    Plan of utterance `b`, built on the host in integers and float64:
+
+    - One Philox4x32-10 block: key = the utterance's 64-bit key (low word, high word, as `dither_noise.h` splits it),
+      counter = `(0, 0, 0, 0x4D495831)`. `dither_noise.h` and `specaug_rule.h` leave the fourth counter word zero, so
+      this counter differs from every one of theirs.
+    - Output words `x0..x3`, with `K` clips and `L_j` the length of clip `j`:
+      - clip `j = (uint64(x0) · K) >> 32`
+      - start `s = (uint64(x1) · L_j) >> 32`
+      - `snr = lo + (hi − lo) · (float64(x2) · 2⁻³²)`, each operation rounded by itself. It is exactly `lo` when
+        `lo == hi`.
+      - `applied = float64(x3) · 2⁻³² < prob`
+      - ratio `r = math.pow(10.0, snr / 10.0)`, one scalar call per utterance.
+
+    Gain, on the device, float64, one lane per utterance:
+
+    - `Ps` is the mean power of the utterance's samples. `Pn` is that of the whole clip `j`.
+    - If `applied`, `Ps > 0` and `Pn > 0`, then `g = sqrt(Ps / (Pn · r))`. The product, the quotient and the root are
+      each rounded by itself.
+    - Otherwise `g = 0.0`. The comparisons are false for NaN.
+
+    Mix:
+
+    - For `0 ≤ t < n`: `y[t] = T(float64(x[t]) + g · float64(z[o_j + ((s + t) mod L_j)]))`. `z` is the noise bank;
+      `o_j` and `L_j` are clip `j`'s offset and length in it. Product and sum are rounded separately, and there is one
+      rounding to `T`.
+    - `T` is float32 for float32 and int16 signals, and float64 for float64 signals.
+    - When `g` is exactly `0.0` the utterance is copied. Float input goes byte for byte. int16 is widened.
+    - A clip shorter than the utterance wraps as often as needed.
+    - Float samples outside every utterance keep their values. For int16 input only the utterance spans are defined.
+    - `+inf` anywhere is only promised not to disturb other utterances.
+
+    So a silent or NaN utterance, a silent or NaN clip and an utterance not chosen are all copied.  `Pn` is the power of
+    the whole clip (Kaldi's rule), computed once per device (:func:`clip_power`).  Refused with ``ValueError`` before
+    any device work: a bad `snr_db` or `prob`, an empty bank or clip, mixed clip dtypes, a signal that is not a 1-D GPU
+    tensor of the three dtypes, utterances outside the signal, a plan of the wrong length or with `clip` or `start`
+    out of range, a batch needing more than 2^31 - 1 blocks.  Reverberation and speed perturbation are other stages;
+    there is no streaming form, because the gain needs the whole utterance's energy.
+    """
+
+    aliases = {"add_noise", "additive_noise", "mix_noise"}
+
+    def __init__(self, clips, snr_db=(5.0, 20.0), prob: float = 1.0, seed: Optional[int] = None):
+        super().__init__()
+        self.snr_db = self._check_snr(snr_db)
+        if isinstance(prob, (bool, np.bool_)) or not isinstance(prob, numbers.Real) or not 0.0 <= float(prob) <= 1.0:
+            raise ValueError(f"prob must lie in [0, 1], not {prob!r}")
+        self.prob = float(prob)
+        if isinstance(clips, (str, bytes, os.PathLike)) or not hasattr(clips, "__len__") or hasattr(clips, "dtype"):
+            raise ValueError("clips must be a sequence of 1-D arrays, 1-D tensors or paths")
+        if len(clips) == 0:
+            raise ValueError("the noise bank is empty: clips must hold at least one clip")
+        read = [self._read_clip(k, clip) for k, clip in enumerate(clips)]
+        kinds = {clip.dtype for clip in read}
+        if len(kinds) > 1:
+            raise ValueError(f"the clips have mixed dtypes ({', '.join(sorted(str(kind) for kind in kinds))}): one of "
+                             "float32, float64 or int16 for all")
+        lengths = np.asarray([len(clip) for clip in read], dtype=np.int64)
+        self._bank = np.ascontiguousarray(np.concatenate(read))
+        self._clip_lengths = lengths
+        self._clip_offsets = (np.cumsum(lengths) - lengths).astype(np.int64)
+        for table in (self._bank, self._clip_lengths, self._clip_offsets):
+            table.flags.writeable = False
+        self._given_seed = seed
+        self._seed = _seed_state(seed)
+        self._on_device = {}  # device index -> [bank, its table (offsets, lengths, chunk bases), Pn or None]
+
+    @staticmethod
+    def _check_snr(snr_db):
+        def number(v):
+            return isinstance(v, numbers.Real) and not isinstance(v, (bool, np.bool_)) and math.isfinite(float(v))
+
+        if number(snr_db):
+            return (float(snr_db), float(snr_db))
+        try:
+            lo, hi = snr_db
+        except (TypeError, ValueError):
+            raise ValueError(f"snr_db must be a finite number or a pair (lo, hi), not {snr_db!r}") from None
+        if not (number(lo) and number(hi)) or float(lo) > float(hi):
+            raise ValueError(f"snr_db must be a finite number or a pair (lo, hi) with lo <= hi, not {snr_db!r}")
+        return (float(lo), float(hi))
+
+    @staticmethod
+    def _read_clip(k, clip):
+        if isinstance(clip, (str, os.PathLike)):
+            from .util import read_signal
+
+            clip = read_signal(os.fspath(clip), dtype=None)
+        elif hasattr(clip, "detach") and hasattr(clip, "cpu"):  # a tensor, wherever it lies
+            clip = clip.detach().cpu().numpy()
+        clip = np.asarray(clip)
+        if clip.ndim != 1:
+            raise ValueError(f"clip {k} has shape {tuple(clip.shape)}: a clip is 1-D")
+        if clip.size == 0:
+            raise ValueError(f"clip {k} is empty")
+        if clip.dtype not in (np.float32, np.float64, np.int16):
+            raise ValueError(f"clip {k} is {clip.dtype}: a clip is float32, float64 or int16")
+        return clip
+
+    @property
+    def seed(self) -> Optional[int]:
+        """the `seed` this object was built with"""
+        return self._given_seed
+
+    num_clips = property(lambda self: len(self._clip_lengths), doc="K, the clips of the bank")
+    clip_offsets = property(lambda self: self._clip_offsets, doc="int64 per clip: its first sample in the bank")
+    clip_lengths = property(lambda self: self._clip_lengths, doc="int64 per clip: its samples")
+    bank = property(lambda self: self._bank, doc="the clips back to back, in their dtype (host copy, read-only)")
+
+    def __repr__(self) -> str:
+        # (what the object was built with and nothing of where it lies: a test id made of it is the same in every run)
+        return (f"AddNoise(clips=<{self.num_clips} of {self._bank.dtype}>, snr_db={self.snr_db!r}, prob={self.prob!r}, "
+                f"seed={self._given_seed!r})")
+
+    # -- the plan ---------------------------------------------------------------------------------------------------
+
+    def _keys(self, B: int, seeds) -> np.ndarray:
+        if seeds is None:
+            keys = np.empty(B, dtype=np.uint64)
+            for b in range(B):
+                self._seed = keys[b] = _next_key(self._seed)
+            return keys
+        if len(seeds) != B:
+            raise ValueError("one seed per utterance")
+        return dither_keys(seeds)
+
+    def plan(self, B: int, seeds=None, clips=None, snr_db=None) -> NoisePlan:
+        """The plan of `B` utterances as numpy arrays: ``clip``, ``start``, ``snr_db``, ``ratio``, ``applied``
+
+        With `seeds`, one integer per utterance, utterance b's plan is that of the first call of ``AddNoise(...,
+        seed=seeds[b])`` and this object's sequence is not touched; with ``seeds=None`` the sequence advances `B`
+        times.  `clips` and `snr_db`, one value per utterance, take the place of those draws (``start`` is still drawn,
+        against the chosen clip's length).  :func:`apply_packed` applies a plan as given (``plan=``), so one plan can
+        go on two views.
+        """
+        if isinstance(B, (bool, np.bool_)) or not isinstance(B, numbers.Integral) or B < 0:
+            raise ValueError(f"B must be a non-negative integer, not {B!r}")
+        B = int(B)
+        given_clips = given_snr = None
+        if clips is not None:
+            given_clips = np.asarray(clips).reshape(-1)
+            if len(given_clips) != B or (B and given_clips.dtype.kind not in "iu"):
+                raise ValueError("clips: one clip index per utterance")
+            given_clips = given_clips.astype(np.int64)
+            if B and (given_clips.min() < 0 or given_clips.max() >= self.num_clips):
+                raise ValueError(f"clips: an index outside [0, {self.num_clips})")
+        if snr_db is not None:
+            given_snr = np.asarray(snr_db, dtype=np.float64).reshape(-1)
+            if len(given_snr) != B or not np.isfinite(given_snr).all():
+                raise ValueError("snr_db: one finite value per utterance")
+        x0, x1, x2, x3 = _mix_draws(self._keys(B, seeds))
+        clip = _mix_pick(x0, np.uint64(self.num_clips)) if given_clips is None else given_clips
+        start = _mix_pick(x1, self._clip_lengths[clip].astype(np.uint64))
+        lo, hi = self.snr_db
+        # (every operation on float64 arrays rounds by itself; (hi - lo) is +0.0 where lo == hi, so snr is lo there)
+        snr = (lo + (hi - lo) * (x2.astype(np.float64) * 2.0 ** -32)) if given_snr is None else given_snr
+        applied = x3.astype(np.float64) * 2.0 ** -32 < self.prob
+        # one scalar call per utterance: an array call may round differently
+        ratio = np.fromiter((math.pow(10.0, float(v) / 10.0) for v in snr), dtype=np.float64, count=B)
+        return NoisePlan(clip.astype(np.int64), start, np.asarray(snr, dtype=np.float64), ratio, applied)
+
+    def _check_plan(self, plan, B: int) -> NoisePlan:
+        try:
+            clip, start, snr, ratio, applied = (np.asarray(v).reshape(-1) for v in plan)
+        except (TypeError, ValueError):
+            raise ValueError("plan must hold clip, start, snr_db, ratio and applied, as plan() returns them") from None
+        if any(len(v) != B for v in (clip, start, snr, ratio, applied)):
+            raise ValueError(f"the plan is not one of {B} utterances")
+        if B and (clip.dtype.kind not in "iu" or start.dtype.kind not in "iu"):
+            raise ValueError("the plan's clip and start are integers")
+        clip, start = clip.astype(np.int64), start.astype(np.int64)
+        if B and (clip.min() < 0 or clip.max() >= self.num_clips):
+            raise ValueError(f"the plan names a clip outside [0, {self.num_clips})")
+        if B and (start.min() < 0 or (start >= self._clip_lengths[clip]).any()):
+            raise ValueError("the plan has a start outside its clip")
+        return NoisePlan(clip, start, snr.astype(np.float64), ratio.astype(np.float64), applied.astype(bool))
+
+    # -- the device side ----------------------------------------------------------------------------------------------
+
+    @staticmethod
+    def _check_packed(signal, offsets, lengths):
+        """(offsets, lengths, B) on the host, or the ``ValueError`` -- nothing here needs a device"""
+        import torch
+
+        if not _is_gpu_tensor(signal) or signal.dim() != 1:
+            raise ValueError("signal must be a 1-D GPU tensor")
+        if signal.dtype not in (torch.float32, torch.float64, torch.int16):
+            raise ValueError("signal must be float32, float64 or int16")
+        offs_h = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        lens_h = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        B = len(lens_h)
+        if len(offs_h) != B:
+            raise ValueError("one offset per length")
+        if B and (offs_h.min() < 0 or lens_h.min() < 0 or int((offs_h + lens_h).max()) > signal.numel()):
+            raise ValueError("the utterances lie outside signal")
+        return offs_h, lens_h, B
+
+    @staticmethod
+    def _chunk_bases(lens_h):
+        """(chunk base per segment, chunks in all), refusing more than 2^31 - 1 blocks of the energy kernel"""
+        chunks = _mix_chunks(lens_h).astype(np.int64).reshape(-1)
+        ends = np.cumsum(chunks)
+        total = int(ends[-1]) if len(chunks) else 0
+        if -(-total // _MIX_ENERGY_WAVES) > _MIX_MAX_BLOCKS:
+            raise ValueError("the batch needs more than 2^31 - 1 blocks in one launch of the energy kernel: split it")
+        return (ends - chunks).astype(np.int64), total
+
+    @staticmethod
+    def _apply_calls(lens_h):
+        """[(lo, hi, longest)] of the apply kernel's launches, refusing one of more than 2^31 - 1 blocks"""
+        calls = []
+        for lo in range(0, len(lens_h), _MIX_MAX_UTTS):
+            hi = min(len(lens_h), lo + _MIX_MAX_UTTS)
+            longest = int(lens_h[lo:hi].max())
+            blocks_x = -(-(longest + _MIX_VEC - 1) // _MIX_TILE) if longest else 0
+            if blocks_x * (hi - lo) > _MIX_MAX_BLOCKS:
+                raise ValueError("the batch needs more than 2^31 - 1 blocks in one launch of the apply kernel: split it")
+            calls.append((lo, hi, longest))
+        return calls
+
+    @staticmethod
+    def _suffix(dtype) -> str:
+        return {"float32": "f32", "float64": "f64", "int16": "i16"}[str(dtype).replace("torch.", "")]
+
+    def _chunk_sums(self, torch, lib, signal, table, B, total):
+        """the chunk sums of the B segments of `signal` that rows 0..2 of `table` (offsets, lengths, chunk bases) name"""
+        partials = torch.empty((total,), dtype=torch.float64, device=signal.device)
+        fn = getattr(lib, "pds_mix_chunk_energy_" + self._suffix(signal.dtype))
+        rc = fn(signal.data_ptr(), table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(), B, total,
+                partials.data_ptr(), torch.cuda.current_stream(signal.device).cuda_stream)
+        _native.check_stages5(rc, "pds_mix_chunk_energy")
+        return partials
+
+    def _bank_on(self, device):
+        torch = _native.require_device()
+        key = torch.device(device).index if device is not None else None
+        if key is None:
+            key = torch.cuda.current_device()
+        got = self._on_device.get(key)
+        if got is None:
+            dev = torch.device("cuda", key)
+            bases, _ = self._chunk_bases(self._clip_lengths)
+            table = np.stack([self._clip_offsets, self._clip_lengths, bases])
+            got = self._on_device[key] = [torch.from_numpy(self._bank.copy()).to(dev), torch.from_numpy(table).to(dev),
+                                          None]
+        return got
+
+    def clip_power(self, device=None):
+        """float64 GPU tensor ``[K]``: the mean power `Pn` of every clip of the bank, computed once per device"""
+        torch = _native.require_device()
+        entry = self._bank_on(device)
+        if entry[2] is None:
+            lib = _native.stages5_lib()
+            bank, table, _ = entry
+            K = self.num_clips
+            _, total = self._chunk_bases(self._clip_lengths)
+            with torch.cuda.device(bank.device):
+                partials = self._chunk_sums(torch, lib, bank, table, K, total)
+                pn = torch.empty((K,), dtype=torch.float64, device=bank.device)
+                rc = lib.pds_mix_gain(partials.data_ptr(), table[2].data_ptr(), table[1].data_ptr(), K, 1, None, None,
+                                      None, None, 0, pn.data_ptr(), torch.cuda.current_stream(bank.device).cuda_stream)
+                _native.check_stages5(rc, "pds_mix_gain")
+            entry[2] = pn
+        return entry[2]
+
+    def energy_packed(self, signal, offsets, lengths):
+        """float64 GPU tensor ``[B]``: the segment energy `E` of every utterance of a packed GPU buffer, as the
+        definition sums it (utterance b is ``signal[offsets[b] : offsets[b] + lengths[b]]``)"""
+        offs_h, lens_h, B = self._check_packed(signal, offsets, lengths)
+        bases, total = self._chunk_bases(lens_h)
+        torch = _native.require_device()
+        lib = _native.stages5_lib()
+        signal = signal.contiguous()
+        out = torch.empty((B,), dtype=torch.float64, device=signal.device)
+        if not B:
+            return out
+        table = torch.as_tensor(np.stack([offs_h, lens_h, bases])).to(signal.device)
+        with torch.cuda.device(signal.device):
+            partials = self._chunk_sums(torch, lib, signal, table, B, total)
+            rc = lib.pds_mix_gain(partials.data_ptr(), table[2].data_ptr(), table[1].data_ptr(), B, 0, None, None, None,
+                                  None, 0, out.data_ptr(), torch.cuda.current_stream(signal.device).cuda_stream)
+            _native.check_stages5(rc, "pds_mix_gain")
+        return out
+
+    def apply_packed(self, signal, offsets, lengths, seeds=None, plan=None, return_gains: bool = False):
+        """Mix noise into every utterance of a packed GPU buffer (see ``compute_packed``): three launches, one upload,
+        no synchronisation
+
+        `signal`: a 1-D GPU tensor of float32, float64 or int16 (16-bit PCM is widened on the device, exactly, and
+        gives a float32 result); utterance b is ``signal[offsets[b] : offsets[b] + lengths[b]]``.  `seeds` as for
+        :func:`plan`; a `plan` is applied as given (and no seed is used).  Returns a new tensor of `signal`'s length;
+        with `return_gains` also the float64 gains ``[B]`` on the device.  For float input, samples outside every
+        utterance keep their values; for int16 input only the utterance spans are defined.
+        """
+        import torch
+
+        offs_h, lens_h, B = self._check_packed(signal, offsets, lengths)
+        if plan is None:
+            if seeds is not None and len(seeds) != B:
+                raise ValueError("one seed per utterance")
+        else:
+            plan = self._check_plan(plan, B)
+        bases, total = self._chunk_bases(lens_h)
+        calls = self._apply_calls(lens_h)
+        if plan is None:
+            plan = self.plan(B, seeds=seeds)
+        torch = _native.require_device()
+        lib = _native.stages5_lib()
+        signal = signal.contiguous()
+        if signal.dtype == torch.int16:
+            out = torch.empty(signal.shape, dtype=torch.float32, device=signal.device)
+        elif B and np.array_equal(offs_h, np.cumsum(lens_h) - lens_h) and int(lens_h.sum()) == signal.numel():
+            out = torch.empty_like(signal)  # (the utterances cover the buffer: every sample is written)
+        else:
+            out = signal.clone()  # gaps between utterances keep their contents
+        gains = torch.empty((B,), dtype=torch.float64, device=signal.device)
+        if not B:
+            return (out, gains) if return_gains else out
+        bank, bank_table, _ = self._bank_on(signal.device)
+        pn = self.clip_power(signal.device)
+        # everything the kernels need of the batch goes up in one copy (a ratio's bits travel as int64)
+        table = torch.as_tensor(np.stack([
+            offs_h, lens_h, bases, self._clip_offsets[plan.clip], self._clip_lengths[plan.clip], plan.start,
+            np.ascontiguousarray(plan.ratio).view(np.int64), plan.applied.astype(np.int64), plan.clip,
+        ])).to(signal.device)
+        fn = getattr(lib, f"pds_mix_apply_{self._suffix(signal.dtype)}_{self._suffix(bank.dtype)}")
+        with torch.cuda.device(signal.device):
+            stream = torch.cuda.current_stream(signal.device).cuda_stream
+            partials = self._chunk_sums(torch, lib, signal, table, B, total)
+            rc = lib.pds_mix_gain(partials.data_ptr(), table[2].data_ptr(), table[1].data_ptr(), B, 2, table[8].data_ptr(),
+                                  table[6].data_ptr(), table[7].data_ptr(), pn.data_ptr(), self.num_clips,
+                                  gains.data_ptr(), stream)
+            _native.check_stages5(rc, "pds_mix_gain")
+            for lo, hi, longest in calls:
+                rc = fn(signal.data_ptr(), table[0, lo:].data_ptr(), table[1, lo:].data_ptr(), bank.data_ptr(),
+                        table[3, lo:].data_ptr(), table[4, lo:].data_ptr(), table[5, lo:].data_ptr(),
+                        gains[lo:].data_ptr(), hi - lo, longest, out.data_ptr(), stream)
+                _native.check_stages5(rc, "pds_mix_apply")
+        return (out, gains) if return_gains else out
+
+    def apply(self, signal, axis: Optional[int] = None, in_place: bool = False):
+        """Noise on a signal, or on every vector along `axis` (default: the last) of an array of more dimensions
+
+        A 1-D signal is one utterance; with more dimensions every vector along `axis` is an utterance of its own draw,
+        and the seed sequence advances once per vector, in C order of the other axes.  numpy arrays go to the device
+        and come back in their dtype; GPU tensors stay (float32 and float64 as they are, any other dtype through
+        float64).
+        """
+        t, was_gpu, dtype = _device_copy(signal)
+        if t.dim() == 0:
+            raise ValueError("AddNoise applies to signals of at least one dimension")
+        if t.numel() == 0:
+            return _finish(t.clone(), was_gpu, dtype, signal, in_place)
+        ax = t.dim() - 1 if axis is None else int(axis) % t.dim()
+        work = t.movedim(ax, -1).contiguous()
+        n = work.shape[-1]
+        rows = work.numel() // n
+        out = self.apply_packed(work.reshape(-1), np.arange(rows, dtype=np.int64) * n, np.full(rows, n, dtype=np.int64))
+        out = out.reshape(work.shape).movedim(-1, ax)
+        if was_gpu and in_place and out.dtype == signal.dtype:
+            signal.copy_(out)
+            return signal
+        return _finish(out.contiguous(), was_gpu, dtype, signal, in_place)
