@@ -150,6 +150,19 @@ extern unsigned long long *g_stamp_buf;  // (stft_fast.hip: pds_debug_set_stamp_
 #ifndef PDS_PF_ILV
 #define PDS_PF_ILV 0
 #endif
+// Items at a signal end where one bounce suffices (in-lane front end): 1 = reflected indices and loads in straight-line
+// code, a batch of rows in flight at once; 0 = the rolled gather through LDS (one memory round trip per row) that
+// general reflection keeps
+#ifndef PDS_EDGE_STRAIGHT
+#define PDS_EDGE_STRAIGHT 1
+#endif
+// ... in the instantiations of at most this many rows per frame.  The straight-line code is 32 bytes per row and flow
+// (twice that with fused pre-emphasis) in each of the library's 285 instantiations, whose device code is capped
+// (tests/test_resources.py): the 50- to 64-row instantiations (N = 1024, and the full-size buckets of N = 2048 / 4096)
+// would take 0.4 MB more and keep the rolled gather.
+#ifndef PDS_EDGE_STRAIGHT_ROWS
+#define PDS_EDGE_STRAIGHT_ROWS 38
+#endif
 }  // namespace pds
 
 // Mirror-image bins of the power spectrum stored from their lowest address up (one address register + immediate

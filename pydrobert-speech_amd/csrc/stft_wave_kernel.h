@@ -989,6 +989,13 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
         wmode = __builtin_amdgcn_readfirstlane(__any(mode == 2) ? 2 : (__any(mode == 1) ? 1 : 0));
       }
 
+      // (the straight-line gather of the edge items: where its rows fit the library's code budget, see stft_switches.h)
+      constexpr bool EDGE_STRAIGHT = PDS_EDGE_STRAIGHT != 0 && NROWS <= PDS_EDGE_STRAIGHT_ROWS;
+      // (opaque: compared as `wmode == 1` beside `wmode == 0` the compiler makes a switch of the two, and the regular
+      // item reaches its loads through four branches instead of two)
+      int wmode1 = wmode;
+      asm("" : "+s"(wmode1));
+      [[maybe_unused]] const bool one_bounce = wmode1 == 1;
       float a[N1];
       if (PF && pf_ready) {
         // (a regular item by construction: wmode = 0, valid)
@@ -1155,6 +1162,69 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
             for (int n1 = 0; n1 < NROWS; ++n1) a[n1] = preemph_sample(a[n1], (float)xp[n1 * N2 - 1], p.preemph);
           }
         }
+      } else if (EDGE_STRAIGHT && one_bounce) {
+        // An item at a signal end where one bounce suffices (the first and the last chunk of every utterance that is
+        // longer than a frame's overhang): the rows' reflected indices in 32-bit arithmetic, every load of a batch of
+        // rows in flight before the first use, no pass through LDS.  (Rolled, with an LDS write behind every load, the
+        // gather was NROWS memory round trips one after the other where a regular item has one.)  A load takes the
+        // utterance's base from scalar registers and the lane's 32-bit byte offset: launch_wave refuses batches
+        // whose utterances span 4 GB.  Lanes past the frame's end in the last rows read some sample of the signal;
+        // the window (exactly 0 there, applied with the 0 * x = 0 multiply) removes it, and the energy masks it.
+        // PRE: the predecessor of the REFLECTED index is loaded beside the sample (sample 0 has none and stays).
+        // Batches: what a row holds in flight beside a[] -- nothing, its predecessor, a float64 value, or both.
+        const char *xb = reinterpret_cast<const char *>(x);
+        // (code size: the row's index one add of N2 behind the row before, and 2 n - 1 as one scalar, both opaque --
+        // left to itself the compiler forms every row's index and its complement from a 32-bit literal each)
+        int top = 2 * n - 1, i = start + rho - N2;
+        asm("" : "+s"(top));
+        // (float64 samples with pre-emphasis hold four registers per row in flight: two rows per batch where the
+        // kernel stands at its register limit -- eight lanes per frame, fused deltas: 2 ... 9 spilled otherwise)
+        constexpr int EB = PRE ? (F64S ? ((N2 == 8 || DLT > 0) ? 2 : 4) : 8) : (F64S ? 12 : NROWS);
+#pragma unroll
+        for (int n0 = 0; n0 < NROWS; n0 += EB) {
+          TIN cur[EB];
+          [[maybe_unused]] TIN prv[EB];
+          [[maybe_unused]] unsigned off[EB];
+#pragma unroll
+          for (int k = 0; k < EB; ++k) {
+            if (n0 + k < NROWS) {
+              // without branches: i < 0 -> -1 - i = ~i is max(i, ~i); then u >= n -> 2 n - 1 - u is min(u, top - u).
+              // A lane past the frame's end may lie past 2 n - 1, where that goes negative: any sample will do, 0
+              // (rows below N1 / 2 lie inside the frame: L > N / 2)
+              i += N2;
+              asm("" : "+v"(i));
+              const int u = max(i, ~i);
+              int j = min(u, top - u);
+              if (n0 + k >= N1 / 2) j = max(j, 0);
+              const unsigned o = (unsigned)j * (unsigned)sizeof(TIN);
+              cur[k] = *reinterpret_cast<const TIN *>(xb + o);
+              if constexpr (PRE) {
+                off[k] = o;
+                prv[k] = *reinterpret_cast<const TIN *>(xb + (max(o, (unsigned)sizeof(TIN)) - (unsigned)sizeof(TIN)));
+              }
+            }
+          }
+          if constexpr (PRE || F64S) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int k = 0; k < EB; ++k) {
+            if (n0 + k < NROWS) {
+              if constexpr (!F64S) {
+                float v = (float)cur[k];
+                if constexpr (PRE) v = off[k] ? preemph_sample(v, (float)prv[k], p.preemph) : v;
+                a[n0 + k] = v;
+              } else {
+                TIN w = cur[k];
+                if constexpr (PRE) w = off[k] ? preemph_sample(w, prv[k], (TIN)p.preemph_d) : w;
+                a[n0 + k] = (float)w;
+              }
+            }
+          }
+        }
+        // (the loads are waited for HERE, s_waitcnt vmcnt(0): the regular item's loads are laid out behind this block,
+        // and with loads of this block pending at its end the compiler's wait insertion, which cannot know that the
+        // jump between the two is always taken, made every regular item wait for all its predecessor's stores first:
+        // 1.2 % of the headline launch, profiles/HISTORY.md 14a)
+        __builtin_amdgcn_s_waitcnt(0x0f70);
       } else {
         // (rolled: the lane writes and reads back its own slots, GCH rows per pass through the wave's area)
         float *tmp = wbase;
@@ -1167,10 +1237,10 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
             float v = 0.0f;
             if (idx < L) {
               int i = start + idx;
-              if (wmode == 1) {
+              if (!EDGE_STRAIGHT && wmode == 1) {
                 i = i < 0 ? -1 - i : (i >= n ? 2 * n - 1 - i : i);
               } else {
-                i = (int)reflect_index((int64_t)i, (int64_t)n);
+                i = reflect_index32(i, n);
               }
               if constexpr (!F64S) {
                 v = (float)x[i];

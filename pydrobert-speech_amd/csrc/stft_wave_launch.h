@@ -66,6 +66,12 @@ int32_t launch_wave(const pds_stft_plan *plan, const BatchArgs &a) {
     set_error("stft_batch: too many frame chunks in one call");
     return PDS_ERR_INVALID;
   }
+  // (the edge items' loads address a sample by the utterance's base and a 32-bit byte offset; no frame reaches past
+  // sample max_frames * frame_shift + frame_length)
+  if ((a.max_frames * plan->d.frame_shift + plan->d.frame_length) * (a.in_f64 ? 8 : a.in_i16 ? 2 : 4) > 0xffffffffLL) {
+    set_error("stft_batch: an utterance's samples span more than 4 GB");
+    return PDS_ERR_INVALID;
+  }
   p.chunks_per_utt = (int)chunks;
   // LDS per workgroup: one exchange area per wave, the small tables, and the filter weight
   // rows when they fit.  Workgroup shapes in order of preference -- all CU_WAVES resident as two
