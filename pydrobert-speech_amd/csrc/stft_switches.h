@@ -120,6 +120,13 @@ extern unsigned long long *g_stamp_buf;  // (stft_fast.hip: pds_debug_set_stamp_
 #ifndef PDS_WALK_DPP_FMAC
 #define PDS_WALK_DPP_FMAC 1
 #endif
+// row-segment walk: 1 = items whose four frames all exist, in launches with one round of 12-bin segments and logged
+// features, take a straight-line tail (one scalar compare on the way in, one lane predicate around the four stores);
+// 0 = every item takes the general rounds, which test segment length, round count, use_log and each frame's existence
+// per item (rounds 2-15)
+#ifndef PDS_WALK_FAST_TAIL
+#define PDS_WALK_FAST_TAIL 1
+#endif
 #ifndef PDS_PREEMPH_DPP
 #define PDS_PREEMPH_DPP 1
 #endif

@@ -80,6 +80,7 @@ struct FastParams {
   unsigned waves_rcp;  // ceil(2^32 / waves): ticket / waves as a multiply-high (tickets < 2^28)
   int lds_ticket_off;  // floats from the start of the workgroup's LDS to its ticket counter
   int dyn;             // items handed out by the workgroup's ticket counter (0: static round-robin)
+  int fast_tail;       // row-segment walk: full items of the common shape take the straight-line tail (0: the general rounds)
   const float *mf_tab;  // matrix-pipe front end (MF instantiations): image of MfmaFrontTables
   unsigned long long *stamps;  // diagnostic builds (PDS_STAMPS): [grid waves][12] phase times and absolute times, else null
   // fused statics + deltas launches (DLT instantiations): every wave walks ONE contiguous stretch of the
@@ -509,6 +510,18 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
   const int L = p.L, S = p.S;
   const bool use_power = p.use_power != 0;
   const int col0 = p.include_energy ? 1 : 0;
+  // FTAIL: the row-segment walk has a straight-line tail for full items of the common shape (see the walk).  What makes
+  // an item one is launch-uniform but for the number of its frames that exist: the item needs `fast_need` of them,
+  // four where the launch has the shape and more than any utterance has where it has not (the count the item compares
+  // is the frames from its first to the utterance's last, not capped at four).
+  // (Built into the kernels with float32 features of the geometries in which the 40-filter mel banks have that shape --
+  // 32 x 16, N = 512, and the unpadded 25 x 16 and 30 x 16, N = 400 and 480: some 0.6 KB per instantiation, and the
+  // library's device code is capped, tests/test_resources.py.  At N = 320 and N = 1024 those banks' tables have
+  // segments of 8 and 20 bins.)
+  constexpr bool FTAIL = PDS_WALK_FAST_TAIL != 0 && RSG && DLT == 0 && !STATS && !PF && N2 == 16 &&
+                         (N1 == 32 || N1 == 25 || N1 == 30) && std::is_same<TOUT, float>::value;
+  [[maybe_unused]] const int fast_need =
+      FTAIL && p.fast_tail && p.use_log && p.seg_rounds == 1 && (p.seg_len >> 2) == 3 ? G::GROUPS : 0x7fffffff;
 
   // work items: (utterance, chunk of GROUPS consecutive frames), dealt round-robin to all waves
   // of the grid: the waves of a workgroup take neighbouring chunks, so overlapping samples are
@@ -1793,6 +1806,99 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
       // stores take the global_store_dword voffset, vdata, saddr form; the next frame's row is a scalar add away
       char *const orow0 = reinterpret_cast<char *>(obase);
       const int64_t row_bytes = p.out_stride * (int64_t)sizeof(TOUT);
+      // add up a filter's segments (at most four, on consecutive lanes of one DPP row): lane i takes
+      // lane i + 1's sums where the table says the run continues, then lane i + 2's
+      auto walk_run_sums = [](float &a0, float &a1, float &a2, float &a3, const float m1, const float m2) {
+        auto shl = [](float v, auto ctrl) {
+          return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), decltype(ctrl)::value, 0xf, 0xf, true));
+        };
+#if PDS_WALK_DPP_FMAC
+        // the neighbour's sums as DPP operands of the multiply-adds (the compiler keeps a v_mov_b32_dpp per operand: eight
+        // instructions more per round); lanes without a source add 0 (bound_ctrl); a DPP operand must not be read within
+        // two instructions of its last vector write: one s_nop in front, the rest are four instructions apart
+        (void)shl;
+        asm volatile("s_nop 1\n\t"
+                     "v_fmac_f32_dpp %0, %0, %4 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                     "v_fmac_f32_dpp %1, %1, %4 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                     "v_fmac_f32_dpp %2, %2, %4 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                     "v_fmac_f32_dpp %3, %3, %4 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                     "v_fmac_f32_dpp %0, %0, %5 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                     "v_fmac_f32_dpp %1, %1, %5 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                     "v_fmac_f32_dpp %2, %2, %5 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                     "v_fmac_f32_dpp %3, %3, %5 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:0"
+                     : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(m1), "v"(m2));
+#else
+        a0 = fmaf(shl(a0, inl::Int<0x101>{}), m1, a0);
+        a1 = fmaf(shl(a1, inl::Int<0x101>{}), m1, a1);
+        a2 = fmaf(shl(a2, inl::Int<0x101>{}), m1, a2);
+        a3 = fmaf(shl(a3, inl::Int<0x101>{}), m1, a3);
+        a0 = fmaf(shl(a0, inl::Int<0x102>{}), m2, a0);
+        a1 = fmaf(shl(a1, inl::Int<0x102>{}), m2, a1);
+        a2 = fmaf(shl(a2, inl::Int<0x102>{}), m2, a2);
+        a3 = fmaf(shl(a3, inl::Int<0x102>{}), m2, a3);
+#endif
+      };
+      if constexpr (FTAIL) {
+        // Full item of the common shape (one round of 12-bin segments, logged, all four frames exist): the same
+        // operations in the same order as round_body below, as straight-line code -- none of round_body's uniform tests
+        // (segment length, round count, use_log, a frame-count test and an exec save / restore per frame) is made, and
+        // the four stores share one lane predicate.  Everything but the frame count is folded into fast_need in front of
+        // the item loop, so the way in is one scalar compare.
+        if (frames_here >= fast_need) {
+          const int4 rec = reinterpret_cast<const int4 *>(meta_lds)[lane];
+          const float4 *prow = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(P4) + rec.x);
+          const float4 *wrow = reinterpret_cast<const float4 *>(ellw_lds) + lane;
+          float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+#pragma unroll
+          for (int t4 = 0; t4 < 3; ++t4) {
+            const float4 w = wrow[t4 * 64];
+            const float4 x0 = prow[4 * t4], x1 = prow[4 * t4 + 1], x2 = prow[4 * t4 + 2], x3 = prow[4 * t4 + 3];
+            a0 = fmaf(w.x, x0.x, a0);
+            a1 = fmaf(w.x, x0.y, a1);
+            a2 = fmaf(w.x, x0.z, a2);
+            a3 = fmaf(w.x, x0.w, a3);
+            a0 = fmaf(w.y, x1.x, a0);
+            a1 = fmaf(w.y, x1.y, a1);
+            a2 = fmaf(w.y, x1.z, a2);
+            a3 = fmaf(w.y, x1.w, a3);
+            a0 = fmaf(w.z, x2.x, a0);
+            a1 = fmaf(w.z, x2.y, a1);
+            a2 = fmaf(w.z, x2.z, a2);
+            a3 = fmaf(w.z, x2.w, a3);
+            a0 = fmaf(w.w, x3.x, a0);
+            a1 = fmaf(w.w, x3.y, a1);
+            a2 = fmaf(w.w, x3.z, a2);
+            a3 = fmaf(w.w, x3.w, a3);
+          }
+          // (the record and the segment's fifteen reads first, rolling ahead of the multiply-adds as in round_body's
+          // unrolled arm: without the hint the scheduler issues them in three batches and waits out each)
+          __builtin_amdgcn_sched_group_barrier(0x100, 16, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, 48, 0);
+          walk_run_sums(a0, a1, a2, a3, __int_as_float(rec.y), __int_as_float(rec.z));
+          const float v0 = floor_log(a0, p.log_floor), v1 = floor_log(a1, p.log_floor);
+          const float v2 = floor_log(a2, p.log_floor), v3 = floor_log(a3, p.log_floor);
+          // the four rows' stores under ONE lane predicate (the first lane of a filter's run: column offset >= 0), set
+          // and taken back by hand: written as `if (rec.w >= 0)` the compiler keeps a skip branch around the stores and
+          // moves the logarithms behind it.  Row bases are wave-uniform (scalar adds), the lane adds its 32-bit column
+          // offset: the saddr form of round_body's stores, to the same addresses.
+          const char *const orow1 = orow0 + row_bytes, *const orow2 = orow1 + row_bytes, *const orow3 = orow2 + row_bytes;
+          unsigned long long lanes;
+          asm volatile("v_cmp_lt_i32 vcc, -1, %[off]\n\t"
+                       "s_and_saveexec_b64 %[lanes], vcc\n\t"
+                       "global_store_dword %[off], %[v0], %[r0]\n\t"
+                       "global_store_dword %[off], %[v1], %[r1]\n\t"
+                       "global_store_dword %[off], %[v2], %[r2]\n\t"
+                       "global_store_dword %[off], %[v3], %[r3]\n\t"
+                       "s_mov_b64 exec, %[lanes]"
+                       : [lanes] "=&s"(lanes)
+                       : [off] "v"(rec.w), [v0] "v"(v0), [v1] "v"(v1), [v2] "v"(v2), [v3] "v"(v3), [r0] "s"(orow0),
+                         [r1] "s"(orow1), [r2] "s"(orow2), [r3] "s"(orow3)
+                       : "vcc", "memory");
+          PDS_STAMP(5, 0);  // filter walk
+          wave_sync();
+          continue;
+        }
+      }
       auto round_body = [&](const int rd, float (&logged)[4]) {
         // the lane's walk record, decoded in the prologue: one 16-byte LDS read
         const int4 rec = reinterpret_cast<const int4 *>(meta_lds)[rd * 64 + lane];
@@ -1836,37 +1942,7 @@ __global__ __launch_bounds__(MAXWAVES * 64, MINW) void stft_wave_kernel(const Fa
 #if PDS_PF_WINAT == 0
         read_window();  // (WINLDS: the next item's window slice, behind this round's reads)
 #endif
-        // add up a filter's segments (at most four, on consecutive lanes of one DPP row): lane i takes
-        // lane i + 1's sums where the table says the run continues, then lane i + 2's
-        const float m1 = __int_as_float(rec.y), m2 = __int_as_float(rec.z);
-        auto shl = [](float v, auto ctrl) {
-          return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), decltype(ctrl)::value, 0xf, 0xf, true));
-        };
-#if PDS_WALK_DPP_FMAC
-        // the neighbour's sums as DPP operands of the multiply-adds (the compiler keeps a v_mov_b32_dpp per operand: eight
-        // instructions more per round); lanes without a source add 0 (bound_ctrl); a DPP operand must not be read within
-        // two instructions of its last vector write: one s_nop in front, the rest are four instructions apart
-        (void)shl;
-        asm volatile("s_nop 1\n\t"
-                     "v_fmac_f32_dpp %0, %0, %4 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                     "v_fmac_f32_dpp %1, %1, %4 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                     "v_fmac_f32_dpp %2, %2, %4 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                     "v_fmac_f32_dpp %3, %3, %4 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                     "v_fmac_f32_dpp %0, %0, %5 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                     "v_fmac_f32_dpp %1, %1, %5 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                     "v_fmac_f32_dpp %2, %2, %5 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                     "v_fmac_f32_dpp %3, %3, %5 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:0"
-                     : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(m1), "v"(m2));
-#else
-        a0 = fmaf(shl(a0, inl::Int<0x101>{}), m1, a0);
-        a1 = fmaf(shl(a1, inl::Int<0x101>{}), m1, a1);
-        a2 = fmaf(shl(a2, inl::Int<0x101>{}), m1, a2);
-        a3 = fmaf(shl(a3, inl::Int<0x101>{}), m1, a3);
-        a0 = fmaf(shl(a0, inl::Int<0x102>{}), m2, a0);
-        a1 = fmaf(shl(a1, inl::Int<0x102>{}), m2, a1);
-        a2 = fmaf(shl(a2, inl::Int<0x102>{}), m2, a2);
-        a3 = fmaf(shl(a3, inl::Int<0x102>{}), m2, a3);
-#endif
+        walk_run_sums(a0, a1, a2, a3, __int_as_float(rec.y), __int_as_float(rec.z));
         // the filter's column (bytes), on the first lane of its run; < 0 elsewhere
         const int coff = rec.w;
         const float vals[4] = {a0, a1, a2, a3};

@@ -231,6 +231,9 @@ int32_t launch_wave(const pds_stft_plan *plan, const BatchArgs &a) {
   {
     const char *dyn_env = std::getenv("PDS_STFT_DYN");
     p.dyn = (dyn_env && dyn_env[0] == '0') ? 0 : 1;
+    // (PDS_STFT_FAST_TAIL=0: every item of a row-segment launch takes the general rounds -- the comparison the tests make)
+    const char *ft_env = std::getenv("PDS_STFT_FAST_TAIL");
+    p.fast_tail = (ft_env && ft_env[0] == '0') ? 0 : 1;
   }
   constexpr bool W4 = G::GROUPS == 4;  // the walks over four frames exist for the 16-lane geometries
   const bool seg = SEGOK && (walk == 1 || walk == 3), rsg = W4 && walk == 2, mseg = MSG && walk == 3;
