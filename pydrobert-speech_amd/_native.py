@@ -2,8 +2,8 @@
 kernels outside the fused kernel's instantiation matrix (C ABI: ``include/pds_amd_stages.h``), of
 ``libpds_amd_stages2.so``, the second capped library of stage kernels (C ABI: ``include/pds_amd_stages2.h``), of
 ``libpds_amd_stages3.so``, the third (C ABI: ``include/pds_amd_stages3.h``), of ``libpds_amd_stages4.so``, the
-fourth (C ABI: ``include/pds_amd_stages4.h``), and of ``libpds_amd_stages5.so``, the fifth (C ABI:
-``include/pds_amd_stages5.h``).
+fourth (C ABI: ``include/pds_amd_stages4.h``), of ``libpds_amd_stages5.so``, the fifth (C ABI:
+``include/pds_amd_stages5.h``), and of ``libpds_amd_stages6.so``, the sixth (C ABI: ``include/pds_amd_stages6.h``).
 
 There is deliberately no fallback: if the shared library is missing or a compute call
 is made without a HIP device, an exception is raised.  Nothing in this package computes
@@ -30,6 +30,9 @@ STAGES4_LIB_PATH = os.environ.get("PDS_AMD_STAGES4_LIB") or os.path.join(os.path
 # ... and PDS_AMD_STAGES5_LIB another build of the fifth stages library; without it the file beside the first library
 STAGES5_LIB_PATH = os.environ.get("PDS_AMD_STAGES5_LIB") or os.path.join(os.path.dirname(LIB_PATH),
                                                                          "libpds_amd_stages5.so")
+# ... and PDS_AMD_STAGES6_LIB another build of the sixth stages library; without it the file beside the first library
+STAGES6_LIB_PATH = os.environ.get("PDS_AMD_STAGES6_LIB") or os.path.join(os.path.dirname(LIB_PATH),
+                                                                         "libpds_amd_stages6.so")
 
 PDS_OK = 0
 
@@ -387,8 +390,37 @@ STAGES5_SIGNATURES = {
 STAGES5_SIGNATURES.update({f"pds_mix_apply_{x}_{z}": (c_int32, _MIX_APPLY_ARGS)
                            for x in ("f32", "f64", "i16") for z in ("f32", "f64", "i16")})
 
+_REVERB_SPECTRA_ARGS = [
+    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64,  # d_x, d_off, d_len, d_rir, d_spec_base, B, total_units
+    c_void_p, c_void_p, c_void_p,  # d_twiddle, d_workspace, stream
+]
+
+# name -> (restype, argtypes); every symbol include/pds_amd_stages6.h declares
+STAGES6_SIGNATURES = {
+    "pds_stages6_version": (c_int32, []),
+    "pds_stages6_last_error": (c_char_p, []),
+    "pds_reverb_block_samples": (c_int64, []),
+    "pds_reverb_max_taps": (c_int64, []),
+    "pds_reverb_partitions": (c_int64, [c_int64]),
+    "pds_reverb_spectra_units": (c_int64, [c_int64]),
+    "pds_reverb_convolve_units": (c_int64, [c_int64, c_int64, c_int32]),
+    "pds_reverb_workspace_bytes": (c_int64, [c_int64]),
+    "pds_reverb_twiddles": (c_int32, [c_void_p]),
+    "pds_reverb_spectra_f32": (c_int32, _REVERB_SPECTRA_ARGS),
+    "pds_reverb_spectra_f64": (c_int32, _REVERB_SPECTRA_ARGS),
+    "pds_reverb_spectra_i16": (c_int32, _REVERB_SPECTRA_ARGS),
+    "pds_reverb_convolve": (
+        c_int32,
+        [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64,  # d_x, xtype, d_off, d_len, d_rir, d_spec_base, d_unit_base, B, total_units
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,  # d_workspace, d_h, d_rir_base, d_rir_parts, d_rir_peak, d_rir_tap, d_rir_gain, K
+         c_void_p, c_void_p, c_void_p],  # d_twiddle, d_out, stream
+    ),
+    "pds_reverb_scale": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),  # d_out, d_off, d_len, d_gain, B, max_len, stream
+}
+
 _lib = None
 _stages_lib = None
+_stages6_lib = None
 _stages5_lib = None
 _stages2_lib = None
 _stages3_lib = None
@@ -530,6 +562,28 @@ def stages5_lib() -> ctypes.CDLL:
     return _stages5_lib
 
 
+def stages6_lib() -> ctypes.CDLL:
+    """The loaded sixth stages library; raises :class:`NativeError` if it has not been built"""
+    global _stages6_lib
+    if _stages6_lib is None:
+        if not os.path.exists(STAGES6_LIB_PATH):
+            raise NativeError(
+                f"{STAGES6_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
+                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
+            )
+        try:  # (torch's HIP runtime first, as for lib())
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        loaded = ctypes.CDLL(STAGES6_LIB_PATH)
+        for name, (restype, argtypes) in STAGES6_SIGNATURES.items():
+            fn = getattr(loaded, name)  # AttributeError if the .so is stale
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _stages6_lib = loaded
+    return _stages6_lib
+
+
 def last_error() -> str:
     return lib().pds_last_error().decode("utf-8", "replace")
 
@@ -584,6 +638,15 @@ def check_stages5(rc: int, what: str) -> None:
     """:func:`check` for a call into the fifth stages library, which keeps its own error string"""
     if rc != PDS_OK:
         msg = stages5_lib().pds_stages5_last_error().decode("utf-8", "replace")
+        if rc == -1:
+            raise ValueError(f"{what}: {msg}")
+        raise NativeError(f"{what}: {msg} (code {rc})")
+
+
+def check_stages6(rc: int, what: str) -> None:
+    """:func:`check` for a call into the sixth stages library, which keeps its own error string"""
+    if rc != PDS_OK:
+        msg = stages6_lib().pds_stages6_last_error().decode("utf-8", "replace")
         if rc == -1:
             raise ValueError(f"{what}: {msg}")
         raise NativeError(f"{what}: {msg} (code {rc})")

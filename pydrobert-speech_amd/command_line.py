@@ -21,7 +21,11 @@ Same command line and on-disk result as the reference's tool -- a text map of
   the clips are taken to be at the rate of the signal where the stage stands, so it goes behind a ``resample``; with
   ``--seed`` it is seeded per utterance with ``seed + index`` like the dither, so the files do not depend on how the
   corpus was batched and ``--seed 1``, ``--seed 2``, ... give one noisy copy each; without ``--seed`` the object's own
-  seed sequence is used), dither,
+  seed sequence is used), reverberation (``{"name": "reverb", "rirs": ["r1.wav", "r2.npy"], "prob": 0.8}``, at any
+  place in the list, in front of an ``add_noise`` so that the noise is scaled against the reverberated signal: a room
+  impulse response of the bank is convolved with every utterance, ``Reverb.apply_packed``; the responses are taken to be
+  at the rate of the signal where the stage stands; seeded like ``add_noise``; its result is float32, so the stages
+  behind it see float32), dither,
   pre-emphasis (fused into the frame loader when it is the last pre-processor), the fused STFT/filter-bank kernel, then each
   post-processor over the packed rows (a ``Cepstra`` -- ``--postprocess '[{"name": "mfcc", "num_ceps": 13}]'`` --
   works row by row, so the whole batch is one call and one launch, and the row offsets stay as they are; a
@@ -64,7 +68,7 @@ from .alias import alias_factory_subclass_from_arg
 from .compute import FrameComputer
 from .post import (PCEN, PLP, Cepstra, Deltas, EnergyVAD, PostProcessor, SlidingCMVN, SpecAugment, Stack, Standardize,
                    refuse_log_computer)
-from .pre import AddNoise, Dither, Preemphasize, PreProcessor, Resample
+from .pre import AddNoise, Dither, Preemphasize, PreProcessor, Resample, Reverb
 from .util import SIGNAL_SOURCES, read_signal
 
 __all__ = ["FeatureDirWriter", "signals_to_torch_feat_dir"]
@@ -108,7 +112,8 @@ def _parse(args):
     ap.add_argument("--force-as", default=None, choices=sorted(SIGNAL_SOURCES),
                     help="read every path as this type instead of going by its name")
     ap.add_argument("--seed", type=_nonneg, default=None,
-                    help="seed for dithering, noise mixing (add_noise) and SpecAugment: utterance i gets seed + i")
+                    help="seed for dithering, noise mixing (add_noise), reverberation (reverb) and SpecAugment: utterance i "
+                         "gets seed + i")
     ap.add_argument("--file-prefix", default="")
     ap.add_argument("--file-suffix", default=".pt")
     ap.add_argument("--num-workers", type=_nonneg, default=0,
@@ -138,7 +143,7 @@ class FeatureDirWriter:
                  file_suffix: str = ".pt", manifest=None, precision: str = "float32", staging_ring: bool = False,
                  seeded: bool = True):
         for pre in preprocessors:
-            if not isinstance(pre, (AddNoise, Dither, Preemphasize, Resample)):
+            if not isinstance(pre, (AddNoise, Dither, Preemphasize, Resample, Reverb)):
                 raise NotImplementedError(f"pre-processor {type(pre).__name__}")
         if computer is not None and any(isinstance(post, PCEN) for post in postprocessors):
             refuse_log_computer(computer)  # (PCEN takes linear energies)
@@ -194,7 +199,8 @@ class FeatureDirWriter:
             return through_feed
         host = np.concatenate(signals) if offsets[-1] else np.zeros(0, self.dtype)
         packed = torch.from_numpy(host).to("cuda")
-        if packed.dtype == torch.int16 and not (self.pre and isinstance(self.pre[0], (AddNoise, Dither, Resample))):
+        if packed.dtype == torch.int16 and not (
+                self.pre and isinstance(self.pre[0], (AddNoise, Dither, Resample, Reverb))):
             packed = packed.to(torch.float32)  # (uploaded as PCM, widened on the device)
         fused = 0.0
         for k, pre in enumerate(self.pre):
@@ -203,9 +209,9 @@ class FeatureDirWriter:
                 # int16 is widened by the dither's own load)
                 seeds = [self.seed + first_index + b for b in range(len(signals))]
                 packed = pre.apply_packed(packed, offsets[:-1], lengths, seeds=seeds)
-            elif isinstance(pre, AddNoise):
+            elif isinstance(pre, (AddNoise, Reverb)):
                 # every utterance under its own key, seed + its index in the run, as the dither: the same file however
-                # it was batched (PCM that is still int16 is widened by the mix's own load)
+                # it was batched (PCM that is still int16 is widened by the stage's own load; a Reverb's result is float32)
                 seeds = [self.seed + first_index + b for b in range(len(signals))] if self.seeded else None
                 packed = pre.apply_packed(packed, offsets[:-1], lengths, seeds=seeds)
             elif isinstance(pre, Resample):

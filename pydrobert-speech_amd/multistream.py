@@ -336,12 +336,22 @@ class StreamState(_StreamWords):
         self.word[ids] &= 1
 
 
+def _no_streaming_reverb(pre) -> None:
+    """``TypeError`` for a :class:`pre.Reverb`: its scale needs the whole utterance, so it has no per-stream form"""
+    from .pre import Reverb
+
+    if isinstance(pre, Reverb):
+        raise TypeError("StreamBatch: pre.Reverb has no streaming form (its scale needs the whole utterance); "
+                        "reverberate the utterances offline with Reverb.apply_packed")
+
+
 def streaming_preemphasis(preemphasis) -> float:
     """`preemphasis` as :class:`StreamBatch` takes it -- a coefficient, a :class:`pre.Preemphasize` or what
     ``alias_factory_subclass_from_arg(PreProcessor, ...)`` makes one -> the coefficient, 0.0 for none (``None`` or a
     coefficient of 0); ``ValueError`` for anything else"""
     if preemphasis is None:
         return 0.0
+    _no_streaming_reverb(preemphasis)
     if isinstance(preemphasis, (bool, np.bool_)):
         raise ValueError("StreamBatch: preemphasis must be a coefficient or a pre.Preemphasize")
     if not isinstance(preemphasis, (int, float, np.integer, np.floating)):
@@ -367,6 +377,7 @@ def streaming_dither(dither) -> Optional[Tuple[float, Optional[int]]]:
     own (None without one), or None for no dither (``None`` or a coefficient of 0); ``ValueError`` for anything else"""
     if dither is None:
         return None
+    _no_streaming_reverb(dither)
     if isinstance(dither, (bool, np.bool_, int, float, np.integer, np.floating)):
         raise ValueError("StreamBatch: dither must be a pre.Dither (a bare number says nothing about the seed)")
     try:

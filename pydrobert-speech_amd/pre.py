@@ -18,6 +18,9 @@ changes a signal's length.
 ``AddNoise`` goes beyond the reference too: the waveform augmentation of Kaldi's multi-condition recipes
 (``wav-reverberate --additive-signals --snrs``), a clip of a noise bank added to every utterance of a packed batch at a
 signal-to-noise ratio drawn per utterance, defined exactly so that a numpy model reproduces it.
+
+``Reverb`` is the other half of that tool (``--impulse-response --shift-output --normalize-output``): a room impulse
+response of a bank convolved with every utterance of a packed batch by partitioned overlap-save on the device.
 """
 import abc
 import math
@@ -31,7 +34,8 @@ import numpy as np
 from . import _native
 from .alias import AliasedFactory
 
-__all__ = ["AddNoise", "Dither", "NoisePlan", "PreProcessor", "Preemphasize", "Resample", "dither_keys"]
+__all__ = ["AddNoise", "Dither", "NoisePlan", "PreProcessor", "Preemphasize", "Resample", "Reverb", "ReverbPlan",
+           "dither_keys"]
 
 _AXIS_DEP_MSG = (
     "Specifying axis in preprocessor.apply is deprecated. "
@@ -522,6 +526,53 @@ def _mix_chunks(n):
     return np.where(n > 0, (n + (_MIX_CHUNK - 1)) // _MIX_CHUNK, 0)
 
 
+# what every packed waveform stage checks and counts (AddNoise and Reverb)
+
+def _check_packed(signal, offsets, lengths):
+    """(offsets, lengths, B) on the host, or the ``ValueError`` -- nothing here needs a device"""
+    import torch
+
+    if not _is_gpu_tensor(signal) or signal.dim() != 1:
+        raise ValueError("signal must be a 1-D GPU tensor")
+    if signal.dtype not in (torch.float32, torch.float64, torch.int16):
+        raise ValueError("signal must be float32, float64 or int16")
+    offs_h = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    lens_h = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    B = len(lens_h)
+    if len(offs_h) != B:
+        raise ValueError("one offset per length")
+    if B and (offs_h.min() < 0 or lens_h.min() < 0 or int((offs_h + lens_h).max()) > signal.numel()):
+        raise ValueError("the utterances lie outside signal")
+    return offs_h, lens_h, B
+
+
+def _chunk_bases(lens_h):
+    """(chunk base per segment, chunks in all), refusing more than 2^31 - 1 blocks of the energy kernel"""
+    chunks = _mix_chunks(lens_h).astype(np.int64).reshape(-1)
+    ends = np.cumsum(chunks)
+    total = int(ends[-1]) if len(chunks) else 0
+    if -(-total // _MIX_ENERGY_WAVES) > _MIX_MAX_BLOCKS:
+        raise ValueError("the batch needs more than 2^31 - 1 blocks in one launch of the energy kernel: split it")
+    return (ends - chunks).astype(np.int64), total
+
+
+def _apply_calls(lens_h):
+    """[(lo, hi, longest)] of the apply kernel's launches, refusing one of more than 2^31 - 1 blocks"""
+    calls = []
+    for lo in range(0, len(lens_h), _MIX_MAX_UTTS):
+        hi = min(len(lens_h), lo + _MIX_MAX_UTTS)
+        longest = int(lens_h[lo:hi].max())
+        blocks_x = -(-(longest + _MIX_VEC - 1) // _MIX_TILE) if longest else 0
+        if blocks_x * (hi - lo) > _MIX_MAX_BLOCKS:
+            raise ValueError("the batch needs more than 2^31 - 1 blocks in one launch of the apply kernel: split it")
+        calls.append((lo, hi, longest))
+    return calls
+
+
+def _suffix(dtype) -> str:
+    return {"float32": "f32", "float64": "f64", "int16": "i16"}[str(dtype).replace("torch.", "")]
+
+
 class NoisePlan(NamedTuple):
     """What :func:`AddNoise.plan` draws, one entry per utterance"""
 
@@ -736,50 +787,11 @@ class AddNoise(PreProcessor):
 
     # -- the device side ----------------------------------------------------------------------------------------------
 
-    @staticmethod
-    def _check_packed(signal, offsets, lengths):
-        """(offsets, lengths, B) on the host, or the ``ValueError`` -- nothing here needs a device"""
-        import torch
-
-        if not _is_gpu_tensor(signal) or signal.dim() != 1:
-            raise ValueError("signal must be a 1-D GPU tensor")
-        if signal.dtype not in (torch.float32, torch.float64, torch.int16):
-            raise ValueError("signal must be float32, float64 or int16")
-        offs_h = np.asarray(offsets, dtype=np.int64).reshape(-1)
-        lens_h = np.asarray(lengths, dtype=np.int64).reshape(-1)
-        B = len(lens_h)
-        if len(offs_h) != B:
-            raise ValueError("one offset per length")
-        if B and (offs_h.min() < 0 or lens_h.min() < 0 or int((offs_h + lens_h).max()) > signal.numel()):
-            raise ValueError("the utterances lie outside signal")
-        return offs_h, lens_h, B
-
-    @staticmethod
-    def _chunk_bases(lens_h):
-        """(chunk base per segment, chunks in all), refusing more than 2^31 - 1 blocks of the energy kernel"""
-        chunks = _mix_chunks(lens_h).astype(np.int64).reshape(-1)
-        ends = np.cumsum(chunks)
-        total = int(ends[-1]) if len(chunks) else 0
-        if -(-total // _MIX_ENERGY_WAVES) > _MIX_MAX_BLOCKS:
-            raise ValueError("the batch needs more than 2^31 - 1 blocks in one launch of the energy kernel: split it")
-        return (ends - chunks).astype(np.int64), total
-
-    @staticmethod
-    def _apply_calls(lens_h):
-        """[(lo, hi, longest)] of the apply kernel's launches, refusing one of more than 2^31 - 1 blocks"""
-        calls = []
-        for lo in range(0, len(lens_h), _MIX_MAX_UTTS):
-            hi = min(len(lens_h), lo + _MIX_MAX_UTTS)
-            longest = int(lens_h[lo:hi].max())
-            blocks_x = -(-(longest + _MIX_VEC - 1) // _MIX_TILE) if longest else 0
-            if blocks_x * (hi - lo) > _MIX_MAX_BLOCKS:
-                raise ValueError("the batch needs more than 2^31 - 1 blocks in one launch of the apply kernel: split it")
-            calls.append((lo, hi, longest))
-        return calls
-
-    @staticmethod
-    def _suffix(dtype) -> str:
-        return {"float32": "f32", "float64": "f64", "int16": "i16"}[str(dtype).replace("torch.", "")]
+    # (module-level helpers, shared with Reverb; kept reachable under their old names)
+    _check_packed = staticmethod(_check_packed)
+    _chunk_bases = staticmethod(_chunk_bases)
+    _apply_calls = staticmethod(_apply_calls)
+    _suffix = staticmethod(_suffix)
 
     def _chunk_sums(self, torch, lib, signal, table, B, total):
         """the chunk sums of the B segments of `signal` that rows 0..2 of `table` (offsets, lengths, chunk bases) name"""
@@ -908,6 +920,404 @@ class AddNoise(PreProcessor):
         t, was_gpu, dtype = _device_copy(signal)
         if t.dim() == 0:
             raise ValueError("AddNoise applies to signals of at least one dimension")
+        if t.numel() == 0:
+            return _finish(t.clone(), was_gpu, dtype, signal, in_place)
+        ax = t.dim() - 1 if axis is None else int(axis) % t.dim()
+        work = t.movedim(ax, -1).contiguous()
+        n = work.shape[-1]
+        rows = work.numel() // n
+        out = self.apply_packed(work.reshape(-1), np.arange(rows, dtype=np.int64) * n, np.full(rows, n, dtype=np.int64))
+        out = out.reshape(work.shape).movedim(-1, ax)
+        if was_gpu and in_place and out.dtype == signal.dtype:
+            signal.copy_(out)
+            return signal
+        return _finish(out.contiguous(), was_gpu, dtype, signal, in_place)
+
+
+# ---- Reverb -----------------------------------------------------------------------------------------------------------
+
+_REVERB_BLOCK, _REVERB_FFT = 512, 1024  # taps of a partition, points of a transform (csrc/reverb_rule.h)
+_REVERB_MAX_TAPS = 1 << 20  # taps of a room impulse response (REVERB_MAX_TAPS)
+_REVERB_HALVES = 8  # units of a block of the transform kernels (REVERB_HALVES)
+_REVERB_MAX_BLOCKS = (1 << 31) - 1  # blocks of one launch (REVERB_MAX_BLOCKS)
+_REVERB_COUNTER = (0, 0, 0, 0x52495231)  # the counter of the plan's Philox block (REVERB_COUNTER_0 .. REVERB_COUNTER_3)
+
+
+def _philox_draws(keys: np.ndarray, counter):
+    """x0..x3 of one Philox4x32-10 block on `counter` under every key of `keys` (uint64): four uint64 arrays of 32-bit
+    values"""
+    keys = np.asarray(keys, dtype=np.uint64)
+    k0, k1 = keys & _U32, keys >> _S32
+    c = [np.full(keys.shape, word, dtype=np.uint64) for word in counter]
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> _S32) ^ c[1] ^ k0, p1 & _U32, (p0 >> _S32) ^ c[3] ^ k1, p0 & _U32]
+        k0 = (k0 + np.uint64(0x9E3779B9)) & _U32
+        k1 = (k1 + np.uint64(0xBB67AE85)) & _U32
+    return c
+
+
+def _reverb_even(units):
+    return (units + 1) & ~np.int64(1)
+
+
+class ReverbPlan(NamedTuple):
+    """What :func:`Reverb.plan` draws, one entry per utterance"""
+
+    rir: np.ndarray  #: int64, the room impulse response of the bank
+    applied: np.ndarray  #: bool, whether the utterance is reverberated at all
+
+
+class Reverb(PreProcessor):
+    """Convolve a room impulse response of a bank with every utterance: the reverberation half of Kaldi's
+    ``wav-reverberate --impulse-response --shift-output --normalize-output`` (aliases ``reverb``, ``reverberate``,
+    ``rir``)
+
+    `rirs` is a non-empty sequence of room impulse responses, each a 1-D array, a 1-D tensor or a path that the readers
+    of ``util.read_signal`` take (wav, npy, npz, pt), float32, float64 or int16.  `prob` in ``[0, 1]`` is the share of
+    utterances that are reverberated at all; `seed` is as ``Dither``'s: an utterance's key comes from
+    :func:`dither_keys`, and with ``seeds=None`` the object's own sequence advances once per utterance.
+
+    The definition.
+
+    Bank:
+
+    - `K` room impulse responses (RIRs), each one channel of `1 ≤ L_j ≤ 2²⁰` taps, float32, float64 or int16.
+    - Partition size is `B = 512` taps and transform size is `N = 1024`, so `P_j = ceil(L_j / 512)`.
+    - The partition spectra are built on the host in float64: `H_{j,p} = fft(taps[512p : 512p+512]` zero-padded to
+      1024`)`. Each spectrum is rounded once to complex64, uploaded once per device and cached.
+    - The peak is `d_j = ` the first index of `max |h_j[k]|` when `shift_output` is set, else `0`. The taps are compared
+      as float64.
+
+    Plan of utterance `b`, built on the host in integers and float64:
+
+    - One Philox4x32-10 block: key = the utterance's 64-bit key from `pre.dither_keys` (low word, high word), counter =
+      `(0, 0, 0, 0x52495231)`. The fourth word differs from `dither_noise.h`, `specaug_rule.h` and `mix_rule.h`.
+    - RIR `j = (uint64(x0) · K) >> 32`.
+    - `applied = float64(x3) · 2⁻³² < prob`.
+
+    Wet signal, float32 whatever the sample dtype:
+
+    - With `x` zero outside `[0, n)`, `y_full[τ] = Σ_k h[k]·x[τ−k]` and `wet[t] = y_full[t + d]` for `0 ≤ t < n`. The
+      reverberant tail past the last sample is dropped.
+    - It is evaluated by uniformly partitioned overlap-save in float32. The blocks of `y_full` stand on multiples of 512
+      of `τ`, anchored at the utterance's own first sample, not at the buffer's.
+    - float64 samples are rounded to float32 at the load. int16 samples are widened.
+    - A RIR with exactly one non-zero tap `g` at `k0` is a delay and a gain. No transform is taken:
+      `wet[t] = float32(g)·x[t + d − k0]`, one float32 product, `+0.0` where `t + d − k0` lies outside `[0, n)`. A unit
+      impulse therefore returns the samples as loaded.
+    - Independence: an utterance's wet bytes depend on its samples, the RIR and the parameters alone, not on the batch it
+      stands in, its offset in the buffer (aligned or not), its neighbours or the launch. The summation order over `p` is
+      fixed and there are no atomics.
+    - Locality: take `τ` in the block beginning at `b0 = 512·floor(τ/512)`. `wet` at `τ − d` depends, round-off
+      included, only on input samples `b0 − 512·(P+2) ≤ i < b0 + 1536`. Two adjacent real blocks are packed into one
+      complex transform: `ifft(fft(a + i·b)·H) = a⊛h + i·(b⊛h)`. Where that window holds no non-zero sample, the output
+      is exactly `±0.0`.
+
+    Normalisation (`normalize_output`):
+
+    - `Ps` is the mean power of the utterance's samples in their own dtype, `Py` that of the float32 wet signal. Both are
+      the segment energy `E(·, n) / n` of `pds_amd_stages5.h`: the same chunks, lanes and tree.
+    - If `Ps > 0` and `Py > 0`, then `out[t] = float32(float64(wet[t]) · c)` with `c = sqrt(Ps / Py)`. The quotient, the
+      root and the product are each rounded by themselves.
+    - Otherwise the wet signal stands as it is. The comparisons are false for NaN.
+
+    Not applied: a float32 utterance is copied byte for byte, with NaN payloads and signed zeros intact. int16 is widened.
+    float64 is rounded once.
+
+    Gaps and bad samples:
+
+    - Float32 samples outside every utterance keep their bytes. For int16 and float64 input only the utterance spans are
+      defined.
+    - A NaN or infinite sample spoils only the outputs whose window holds it. With `normalize_output` it spoils its own
+      utterance's scale. It never spoils another utterance.
+
+    In a chain with :class:`AddNoise`, ``Reverb`` goes first: ``AddNoise``'s `Ps` is then the reverberated signal's
+    power (Kaldi's early-reverberation energy rule for the SNR is not implemented).  There is no streaming form, because
+    the scale needs the whole utterance; a ``StreamBatch`` handed a ``Reverb`` raises ``TypeError``.  Refused with
+    ``ValueError`` before any device work: a bad `prob`, an empty bank, an empty, multi-channel or too long RIR, a signal
+    that is not a 1-D GPU tensor of the three dtypes, utterances outside the signal, a plan of the wrong length or with
+    `rir` out of range, a batch needing more than 2^31 - 1 blocks.
+    """
+
+    aliases = {"reverb", "reverberate", "rir"}
+
+    def __init__(self, rirs, prob: float = 1.0, shift_output: bool = True, normalize_output: bool = True,
+                 seed: Optional[int] = None):
+        super().__init__()
+        if isinstance(prob, (bool, np.bool_)) or not isinstance(prob, numbers.Real) or not 0.0 <= float(prob) <= 1.0:
+            raise ValueError(f"prob must lie in [0, 1], not {prob!r}")
+        self.prob = float(prob)
+        self.shift_output = bool(shift_output)
+        self.normalize_output = bool(normalize_output)
+        if isinstance(rirs, (str, bytes, os.PathLike)) or not hasattr(rirs, "__len__") or hasattr(rirs, "dtype"):
+            raise ValueError("rirs must be a sequence of 1-D arrays, 1-D tensors or paths")
+        if len(rirs) == 0:
+            raise ValueError("the bank is empty: rirs must hold at least one room impulse response")
+        self._taps = [self._read_rir(k, rir) for k, rir in enumerate(rirs)]
+        self._rir_lengths = np.asarray([len(t) for t in self._taps], dtype=np.int64)
+        self._rir_peaks = np.asarray([self.peak_of(t) if self.shift_output else 0 for t in self._taps], dtype=np.int64)
+        self._rir_parts = -(-self._rir_lengths // _REVERB_BLOCK)
+        self._rir_bases = (np.cumsum(self._rir_parts) - self._rir_parts).astype(np.int64)
+        # a response of one non-zero tap is a delay and a gain: its index (else -1) and the tap as float32
+        single = [np.flatnonzero(t) if np.count_nonzero(t) == 1 else None for t in self._taps]
+        self._rir_taps = np.asarray([-1 if k is None else int(k[0]) for k in single], dtype=np.int64)
+        self._rir_gains = np.asarray([0.0 if k is None else t[int(k[0])] for k, t in zip(single, self._taps)],
+                                     dtype=np.float32)
+        for table in (self._rir_lengths, self._rir_peaks, self._rir_parts, self._rir_bases, self._rir_taps,
+                      self._rir_gains, *self._taps):
+            table.flags.writeable = False
+        self._spectra = None  # complex64 [sum of P_j, 1024], built at the first use
+        self._given_seed = seed
+        self._seed = _seed_state(seed)
+        self._on_device = {}  # device index -> (spectra, table (bases, partitions, peaks), twiddles)
+
+    @staticmethod
+    def _read_rir(k, rir):
+        if isinstance(rir, (str, os.PathLike)):
+            from .util import read_signal
+
+            rir = read_signal(os.fspath(rir), dtype=None)
+        elif hasattr(rir, "detach") and hasattr(rir, "cpu"):  # a tensor, wherever it lies
+            rir = rir.detach().cpu().numpy()
+        rir = np.asarray(rir)
+        if rir.ndim != 1:
+            raise ValueError(f"RIR {k} has shape {tuple(rir.shape)}: a room impulse response is one channel, 1-D")
+        if rir.size == 0:
+            raise ValueError(f"RIR {k} is empty")
+        if rir.size > _REVERB_MAX_TAPS:
+            raise ValueError(f"RIR {k} has {rir.size} taps: at most 2^20")
+        if rir.dtype not in (np.float32, np.float64, np.int16):
+            raise ValueError(f"RIR {k} is {rir.dtype}: a room impulse response is float32, float64 or int16")
+        return np.array(rir, dtype=np.float64)
+
+    @staticmethod
+    def peak_of(taps) -> int:
+        """the first index of ``max |h[k]|``, the taps compared as float64"""
+        return int(np.argmax(np.abs(np.asarray(taps, dtype=np.float64))))
+
+    @staticmethod
+    def partition_spectra(taps) -> np.ndarray:
+        """complex64 ``[P, 1024]``: the spectra of the partitions of 512 taps, formed in float64, rounded once"""
+        taps = np.asarray(taps, dtype=np.float64)
+        parts = -(-len(taps) // _REVERB_BLOCK)
+        padded = np.zeros(parts * _REVERB_BLOCK, dtype=np.float64)
+        padded[: len(taps)] = taps
+        return np.fft.fft(padded.reshape(parts, _REVERB_BLOCK), n=_REVERB_FFT, axis=1).astype(np.complex64)
+
+    @property
+    def seed(self) -> Optional[int]:
+        """the `seed` this object was built with"""
+        return self._given_seed
+
+    num_rirs = property(lambda self: len(self._rir_lengths), doc="K, the room impulse responses of the bank")
+    rir_lengths = property(lambda self: self._rir_lengths, doc="int64 per RIR: its taps")
+    rir_peaks = property(lambda self: self._rir_peaks, doc="int64 per RIR: d, the shift of the output (0 without it)")
+    rir_partitions = property(lambda self: self._rir_parts, doc="int64 per RIR: P, its partitions of 512 taps")
+
+    def __repr__(self) -> str:
+        # (what the object was built with and nothing of where it lies: a test id made of it is the same in every run)
+        return (f"Reverb(rirs=<{self.num_rirs}>, prob={self.prob!r}, shift_output={self.shift_output!r}, "
+                f"normalize_output={self.normalize_output!r}, seed={self._given_seed!r})")
+
+    # -- the plan ---------------------------------------------------------------------------------------------------
+
+    def _keys(self, B: int, seeds) -> np.ndarray:
+        if seeds is None:
+            keys = np.empty(B, dtype=np.uint64)
+            for b in range(B):
+                self._seed = keys[b] = _next_key(self._seed)
+            return keys
+        if len(seeds) != B:
+            raise ValueError("one seed per utterance")
+        return dither_keys(seeds)
+
+    def plan(self, B: int, seeds=None, rirs=None) -> ReverbPlan:
+        """The plan of `B` utterances as numpy arrays: ``rir`` and ``applied``
+
+        With `seeds`, one integer per utterance, utterance b's plan is that of the first call of ``Reverb(...,
+        seed=seeds[b])`` and this object's sequence is not touched; with ``seeds=None`` the sequence advances `B` times.
+        `rirs`, one index per utterance, takes the place of that draw.  :func:`apply_packed` applies a plan as given
+        (``plan=``), so one plan can go on two views.
+        """
+        if isinstance(B, (bool, np.bool_)) or not isinstance(B, numbers.Integral) or B < 0:
+            raise ValueError(f"B must be a non-negative integer, not {B!r}")
+        B = int(B)
+        given = None
+        if rirs is not None:
+            given = np.asarray(rirs).reshape(-1)
+            if len(given) != B or (B and given.dtype.kind not in "iu"):
+                raise ValueError("rirs: one index per utterance")
+            given = given.astype(np.int64)
+            if B and (given.min() < 0 or given.max() >= self.num_rirs):
+                raise ValueError(f"rirs: an index outside [0, {self.num_rirs})")
+        x0, _, _, x3 = _philox_draws(self._keys(B, seeds), _REVERB_COUNTER)
+        rir = ((x0 * np.uint64(self.num_rirs)) >> _S32).astype(np.int64) if given is None else given
+        applied = x3.astype(np.float64) * 2.0 ** -32 < self.prob
+        return ReverbPlan(rir, applied)
+
+    def _check_plan(self, plan, B: int) -> ReverbPlan:
+        try:
+            rir, applied = (np.asarray(v).reshape(-1) for v in plan)
+        except (TypeError, ValueError):
+            raise ValueError("plan must hold rir and applied, as plan() returns them") from None
+        if len(rir) != B or len(applied) != B:
+            raise ValueError(f"the plan is not one of {B} utterances")
+        if B and rir.dtype.kind not in "iu":
+            raise ValueError("the plan's rir is an integer")
+        rir = rir.astype(np.int64)
+        if B and (rir.min() < 0 or rir.max() >= self.num_rirs):
+            raise ValueError(f"the plan names a RIR outside [0, {self.num_rirs})")
+        return ReverbPlan(rir, applied.astype(bool))
+
+    # -- the device side ----------------------------------------------------------------------------------------------
+
+    def layout(self, lengths, plan):
+        """(spectra base per utterance, spectra slots in all, convolve unit base, convolve units in all) of a batch, as
+        csrc/reverb_rule.h counts them; ``ValueError`` where a launch would need more than 2^31 - 1 blocks"""
+        n = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        applied = np.asarray(plan.applied, dtype=bool) & (self._rir_taps[plan.rir] < 0)  # (transformed)
+        d = self._rir_peaks[plan.rir] if len(n) else np.zeros(0, np.int64)
+        some = n > 0
+        last = np.where(some, (n - 1) // _REVERB_BLOCK + 1, 0)
+        spec = np.where(some & applied, _reverb_even(last + 2), 0).astype(np.int64)
+        pairs = np.where(some, (d + n - 1) // _REVERB_FFT - d // _REVERB_FFT + 1, 0)
+        copies = -(-n // _REVERB_FFT)
+        units = np.where(some, _reverb_even(np.where(applied, pairs, copies)), 0).astype(np.int64)
+        spec_total, unit_total = int(spec.sum()), int(units.sum())
+        if max(spec_total, unit_total) > _REVERB_MAX_BLOCKS * _REVERB_HALVES:
+            raise ValueError("the batch needs more than 2^31 - 1 blocks in one launch: split it")
+        return (np.cumsum(spec) - spec).astype(np.int64), spec_total, (np.cumsum(units) - units).astype(np.int64), unit_total
+
+    def spectra(self) -> np.ndarray:
+        """complex64 ``[sum of P_j, 1024]``: the bank's partition spectra, RIR j's from row ``cumsum(P)[j] - P[j]``"""
+        if self._spectra is None:
+            self._spectra = np.concatenate([self.partition_spectra(t) for t in self._taps])
+            self._spectra.flags.writeable = False
+        return self._spectra
+
+    def _bank_on(self, device):
+        torch = _native.require_device()
+        key = torch.device(device).index if device is not None else None
+        if key is None:
+            key = torch.cuda.current_device()
+        got = self._on_device.get(key)
+        if got is None:
+            dev = torch.device("cuda", key)
+            lib = _native.stages6_lib()
+            tw = np.empty(2 * _REVERB_FFT, dtype=np.float32)
+            _native.check_stages6(lib.pds_reverb_twiddles(tw.ctypes.data), "pds_reverb_twiddles")
+            table = np.stack([self._rir_bases, self._rir_parts, self._rir_peaks, self._rir_taps])
+            spectra = torch.from_numpy(np.ascontiguousarray(self.spectra()).view(np.float32).copy())
+            got = self._on_device[key] = (spectra.to(dev), torch.from_numpy(table).to(dev), torch.from_numpy(tw).to(dev),
+                                          torch.from_numpy(self._rir_gains.copy()).to(dev))
+        return got
+
+    def workspace_bytes(self, lengths, plan) -> int:
+        """bytes of the spectra workspace :func:`apply_packed` allocates for a batch"""
+        return self.layout(lengths, plan)[1] * _REVERB_FFT * 8
+
+    def apply_packed(self, signal, offsets, lengths, seeds=None, plan=None, return_wet: bool = False):
+        """Reverberate every utterance of a packed GPU buffer (see ``compute_packed``): one upload of one table, no
+        synchronisation
+
+        `signal`: a 1-D GPU tensor of float32, float64 or int16; utterance b is ``signal[offsets[b] : offsets[b] +
+        lengths[b]]``.  `seeds` as for :func:`plan`; a `plan` is applied as given (and no seed is used).  Returns a new
+        float32 tensor of `signal`'s length; with `return_wet` also the wet signal before the normalisation (the same
+        layout; the output itself without `normalize_output`).  For float32 input, samples outside every utterance keep
+        their bytes; for int16 and float64 input only the utterance spans are defined.
+        """
+        import torch
+
+        offs_h, lens_h, B = _check_packed(signal, offsets, lengths)
+        if plan is None:
+            if seeds is not None and len(seeds) != B:
+                raise ValueError("one seed per utterance")
+        else:
+            plan = self._check_plan(plan, B)
+        chunk_bases, chunk_total = _chunk_bases(lens_h)
+        scale_calls = _apply_calls(lens_h) if B else []
+        if plan is None:
+            plan = self.plan(B, seeds=seeds)
+        spec_base, spec_total, unit_base, unit_total = self.layout(lens_h, plan)
+        torch = _native.require_device()
+        lib = _native.stages6_lib()
+        signal = signal.contiguous()
+        if signal.dtype != torch.float32:
+            out = torch.empty(signal.shape, dtype=torch.float32, device=signal.device)
+        elif B and np.array_equal(offs_h, np.cumsum(lens_h) - lens_h) and int(lens_h.sum()) == signal.numel():
+            out = torch.empty_like(signal)  # (the utterances cover the buffer: every sample is written)
+        else:
+            out = signal.clone()  # gaps between utterances keep their contents
+        if not B or not unit_total:
+            return (out, out.clone()) if return_wet else out
+        h, bank_table, tw, tap_gains = self._bank_on(signal.device)
+        transformed = plan.applied & (self._rir_taps[plan.rir] < 0)
+        normalise = self.normalize_output and bool(plan.applied.any())
+        # everything the kernels need of the batch goes up in one copy (the ratio 1.0 travels as its bits)
+        table = torch.as_tensor(np.stack([
+            offs_h, lens_h, np.where(plan.applied, plan.rir, -1).astype(np.int64), spec_base, unit_base, chunk_bases,
+            np.arange(B, dtype=np.int64), np.full(B, 1.0).view(np.int64), plan.applied.astype(np.int64),
+            np.where(transformed, plan.rir, -1).astype(np.int64),
+        ])).to(signal.device)
+        xtype = {"f32": 0, "f64": 1, "i16": 2}[_suffix(signal.dtype)]
+        with torch.cuda.device(signal.device):
+            stream = torch.cuda.current_stream(signal.device).cuda_stream
+            ws = None
+            if spec_total:
+                ws = torch.empty((spec_total * _REVERB_FFT * 2,), dtype=torch.float32, device=signal.device)
+                fn = getattr(lib, "pds_reverb_spectra_" + _suffix(signal.dtype))
+                rc = fn(signal.data_ptr(), table[0].data_ptr(), table[1].data_ptr(), table[9].data_ptr(),
+                        table[3].data_ptr(), B, spec_total, tw.data_ptr(), ws.data_ptr(), stream)
+                _native.check_stages6(rc, "pds_reverb_spectra")
+            rc = lib.pds_reverb_convolve(signal.data_ptr(), xtype, table[0].data_ptr(), table[1].data_ptr(),
+                                         table[2].data_ptr(), table[3].data_ptr(), table[4].data_ptr(), B, unit_total,
+                                         ws.data_ptr() if ws is not None else None, h.data_ptr(),
+                                         bank_table[0].data_ptr(), bank_table[1].data_ptr(), bank_table[2].data_ptr(),
+                                         bank_table[3].data_ptr(), tap_gains.data_ptr(), self.num_rirs, tw.data_ptr(), out.data_ptr(), stream)
+            _native.check_stages6(rc, "pds_reverb_convolve")
+            wet = out.clone() if return_wet else None
+            if normalise:
+                mix = _native.stages5_lib()
+                energy = (table[0], table[1], table[5])
+
+                def power(x, mode, pn):
+                    partials = torch.empty((chunk_total,), dtype=torch.float64, device=x.device)
+                    fn = getattr(mix, "pds_mix_chunk_energy_" + _suffix(x.dtype))
+                    rc = fn(x.data_ptr(), energy[0].data_ptr(), energy[1].data_ptr(), energy[2].data_ptr(), B,
+                            chunk_total, partials.data_ptr(), stream)
+                    _native.check_stages5(rc, "pds_mix_chunk_energy")
+                    res = torch.empty((B,), dtype=torch.float64, device=x.device)
+                    rc = mix.pds_mix_gain(partials.data_ptr(), energy[2].data_ptr(), energy[1].data_ptr(), B, mode,
+                                          table[6].data_ptr() if mode == 2 else None,
+                                          table[7].view(torch.float64).data_ptr() if mode == 2 else None,
+                                          table[8].data_ptr() if mode == 2 else None,
+                                          pn.data_ptr() if mode == 2 else None, B if mode == 2 else 0, res.data_ptr(),
+                                          stream)
+                    _native.check_stages5(rc, "pds_mix_gain")
+                    return res
+
+                py = power(out, 1, None)
+                gains = power(signal, 2, py)  # sqrt(Ps / (Py * 1.0)) where applied, Ps > 0 and Py > 0, else 0.0
+                for lo, hi, longest in scale_calls:
+                    rc = lib.pds_reverb_scale(out.data_ptr(), table[0, lo:].data_ptr(), table[1, lo:].data_ptr(),
+                                              gains[lo:].data_ptr(), hi - lo, longest, stream)
+                    _native.check_stages6(rc, "pds_reverb_scale")
+        return (out, wet) if return_wet else out
+
+    def apply(self, signal, axis: Optional[int] = None, in_place: bool = False):
+        """Reverberation of a signal, or of every vector along `axis` (default: the last) of an array of more
+        dimensions
+
+        A 1-D signal is one utterance; with more dimensions every vector along `axis` is an utterance of its own draw,
+        and the seed sequence advances once per vector, in C order of the other axes.  numpy arrays go to the device and
+        come back in their dtype; GPU tensors stay, and the result is float32 (float32 and float64 samples as they are,
+        any other dtype through float64).
+        """
+        t, was_gpu, dtype = _device_copy(signal)
+        if t.dim() == 0:
+            raise ValueError("Reverb applies to signals of at least one dimension")
         if t.numel() == 0:
             return _finish(t.clone(), was_gpu, dtype, signal, in_place)
         ax = t.dim() - 1 if axis is None else int(axis) % t.dim()
