@@ -1,11 +1,9 @@
-"""ctypes binding of ``libpds_amd.so`` (C ABI: ``include/pds_amd.h``), of ``libpds_amd_stages.so``, the stage
-kernels outside the fused kernel's instantiation matrix (C ABI: ``include/pds_amd_stages.h``), of
-``libpds_amd_stages2.so``, the second capped library of stage kernels (C ABI: ``include/pds_amd_stages2.h``), of
-``libpds_amd_stages3.so``, the third (C ABI: ``include/pds_amd_stages3.h``), of ``libpds_amd_stages4.so``, the
-fourth (C ABI: ``include/pds_amd_stages4.h``), of ``libpds_amd_stages5.so``, the fifth (C ABI:
-``include/pds_amd_stages5.h``), and of ``libpds_amd_stages6.so``, the sixth (C ABI: ``include/pds_amd_stages6.h``).
+"""ctypes binding of the package's shared libraries: ``libpds_amd.so`` (C ABI: ``include/pds_amd.h``) and the
+stages libraries ``libpds_amd_stages*.so``, each a capped library of stage kernels outside the fused kernel's
+instantiation matrix with a header (``include/pds_amd_stages*.h``) and an error string of its own.  Every one of them
+is a :class:`Library`; ``LIBRARIES`` lists them.
 
-There is deliberately no fallback: if the shared library is missing or a compute call
+There is deliberately no fallback: if a shared library is missing or a compute call
 is made without a HIP device, an exception is raised.  Nothing in this package computes
 features on the CPU.
 """
@@ -14,25 +12,6 @@ import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_int32, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# PDS_AMD_LIB selects another build of the same library (kernel tuning experiments)
-LIB_PATH = os.environ.get("PDS_AMD_LIB") or os.path.join(_HERE, "csrc", "libpds_amd.so")
-# ... and PDS_AMD_STAGES_LIB another build of the stages library
-STAGES_LIB_PATH = os.environ.get("PDS_AMD_STAGES_LIB") or os.path.join(_HERE, "csrc", "libpds_amd_stages.so")
-# ... and PDS_AMD_STAGES2_LIB another build of the second stages library; without it the file beside the first library
-STAGES2_LIB_PATH = os.environ.get("PDS_AMD_STAGES2_LIB") or os.path.join(os.path.dirname(LIB_PATH),
-                                                                         "libpds_amd_stages2.so")
-# ... and PDS_AMD_STAGES3_LIB another build of the third stages library; without it the file beside the first library
-STAGES3_LIB_PATH = os.environ.get("PDS_AMD_STAGES3_LIB") or os.path.join(os.path.dirname(LIB_PATH),
-                                                                         "libpds_amd_stages3.so")
-# ... and PDS_AMD_STAGES4_LIB another build of the fourth stages library; without it the file beside the first library
-STAGES4_LIB_PATH = os.environ.get("PDS_AMD_STAGES4_LIB") or os.path.join(os.path.dirname(LIB_PATH),
-                                                                         "libpds_amd_stages4.so")
-# ... and PDS_AMD_STAGES5_LIB another build of the fifth stages library; without it the file beside the first library
-STAGES5_LIB_PATH = os.environ.get("PDS_AMD_STAGES5_LIB") or os.path.join(os.path.dirname(LIB_PATH),
-                                                                         "libpds_amd_stages5.so")
-# ... and PDS_AMD_STAGES6_LIB another build of the sixth stages library; without it the file beside the first library
-STAGES6_LIB_PATH = os.environ.get("PDS_AMD_STAGES6_LIB") or os.path.join(os.path.dirname(LIB_PATH),
-                                                                         "libpds_amd_stages6.so")
 
 PDS_OK = 0
 
@@ -418,238 +397,79 @@ STAGES6_SIGNATURES = {
     "pds_reverb_scale": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),  # d_out, d_off, d_len, d_gain, B, max_len, stream
 }
 
-_lib = None
-_stages_lib = None
-_stages6_lib = None
-_stages5_lib = None
-_stages2_lib = None
-_stages3_lib = None
-_stages4_lib = None
+
+class Library:
+    """One shared library: its path (from ``variable`` in the environment, which selects another build of the same
+    library, or else ``default``), its ``name -> (restype, argtypes)`` table, the symbol that returns its own error
+    string, and the exceptions of its return codes (``-1`` is a ``ValueError`` everywhere; any code without an entry is
+    a :class:`NativeError` that names it).  Calling the object gives the loaded library."""
+
+    def __init__(self, variable, default, signatures, last_error, errors=()):
+        self.variable = variable
+        self.path = os.environ.get(variable) or default
+        self.signatures = signatures
+        self.errors = {-1: ValueError, **dict(errors)}
+        self._last_error = last_error
+        self._handle = None
+
+    def __call__(self) -> ctypes.CDLL:
+        """The loaded library; raises :class:`NativeError` if it has not been built"""
+        if self._handle is None:
+            if not os.path.exists(self.path):
+                raise NativeError(
+                    f"{self.path} is missing: build it with `python -c 'import __graft_entry__ as g; "
+                    "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
+                )
+            # torch's HIP runtime first where torch is installed: the library's own dependency on libamdhip64
+            # then resolves to the copy already in the process (loaded the other way round, the two runtimes
+            # disagree about the devices)
+            try:
+                import torch  # noqa: F401
+            except ImportError:
+                pass
+            loaded = ctypes.CDLL(self.path)
+            for name, (restype, argtypes) in self.signatures.items():
+                fn = getattr(loaded, name)  # AttributeError if the .so is stale
+                fn.restype = restype
+                fn.argtypes = argtypes
+            self._handle = loaded
+        return self._handle
+
+    def last_error(self) -> str:
+        return getattr(self(), self._last_error)().decode("utf-8", "replace")
+
+    def check(self, rc: int, what: str) -> None:
+        """Raises the exception of a return code other than ``PDS_OK``, with the library's own error string"""
+        if rc != PDS_OK:
+            msg = self.last_error()
+            if rc in self.errors:
+                raise self.errors[rc](f"{what}: {msg}")
+            raise NativeError(f"{what}: {msg} (code {rc})")
 
 
-def lib() -> ctypes.CDLL:
-    """The loaded library; raises :class:`NativeError` if it has not been built"""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise NativeError(
-                f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
-            )
-        # torch's HIP runtime first where torch is installed: the library's own dependency on libamdhip64
-        # then resolves to the copy already in the process (loaded the other way round, the two runtimes
-        # disagree about the devices)
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        loaded = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(loaded, name)  # AttributeError if the .so is stale
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _lib = loaded
-    return _lib
-
-
-def stages_lib() -> ctypes.CDLL:
-    """The loaded stages library; raises :class:`NativeError` if it has not been built"""
-    global _stages_lib
-    if _stages_lib is None:
-        if not os.path.exists(STAGES_LIB_PATH):
-            raise NativeError(
-                f"{STAGES_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
-            )
-        try:  # (torch's HIP runtime first, as for lib())
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        loaded = ctypes.CDLL(STAGES_LIB_PATH)
-        for name, (restype, argtypes) in STAGES_SIGNATURES.items():
-            fn = getattr(loaded, name)  # AttributeError if the .so is stale
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _stages_lib = loaded
-    return _stages_lib
-
-
-def stages2_lib() -> ctypes.CDLL:
-    """The loaded second stages library; raises :class:`NativeError` if it has not been built"""
-    global _stages2_lib
-    if _stages2_lib is None:
-        if not os.path.exists(STAGES2_LIB_PATH):
-            raise NativeError(
-                f"{STAGES2_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
-            )
-        try:  # (torch's HIP runtime first, as for lib())
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        loaded = ctypes.CDLL(STAGES2_LIB_PATH)
-        for name, (restype, argtypes) in STAGES2_SIGNATURES.items():
-            fn = getattr(loaded, name)  # AttributeError if the .so is stale
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _stages2_lib = loaded
-    return _stages2_lib
-
-
-def stages3_lib() -> ctypes.CDLL:
-    """The loaded third stages library; raises :class:`NativeError` if it has not been built"""
-    global _stages3_lib
-    if _stages3_lib is None:
-        if not os.path.exists(STAGES3_LIB_PATH):
-            raise NativeError(
-                f"{STAGES3_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
-            )
-        try:  # (torch's HIP runtime first, as for lib())
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        loaded = ctypes.CDLL(STAGES3_LIB_PATH)
-        for name, (restype, argtypes) in STAGES3_SIGNATURES.items():
-            fn = getattr(loaded, name)  # AttributeError if the .so is stale
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _stages3_lib = loaded
-    return _stages3_lib
-
-
-def stages4_lib() -> ctypes.CDLL:
-    """The loaded fourth stages library; raises :class:`NativeError` if it has not been built"""
-    global _stages4_lib
-    if _stages4_lib is None:
-        if not os.path.exists(STAGES4_LIB_PATH):
-            raise NativeError(
-                f"{STAGES4_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
-            )
-        try:  # (torch's HIP runtime first, as for lib())
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        loaded = ctypes.CDLL(STAGES4_LIB_PATH)
-        for name, (restype, argtypes) in STAGES4_SIGNATURES.items():
-            fn = getattr(loaded, name)  # AttributeError if the .so is stale
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _stages4_lib = loaded
-    return _stages4_lib
-
-
-def stages5_lib() -> ctypes.CDLL:
-    """The loaded fifth stages library; raises :class:`NativeError` if it has not been built"""
-    global _stages5_lib
-    if _stages5_lib is None:
-        if not os.path.exists(STAGES5_LIB_PATH):
-            raise NativeError(
-                f"{STAGES5_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
-            )
-        try:  # (torch's HIP runtime first, as for lib())
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        loaded = ctypes.CDLL(STAGES5_LIB_PATH)
-        for name, (restype, argtypes) in STAGES5_SIGNATURES.items():
-            fn = getattr(loaded, name)  # AttributeError if the .so is stale
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _stages5_lib = loaded
-    return _stages5_lib
-
-
-def stages6_lib() -> ctypes.CDLL:
-    """The loaded sixth stages library; raises :class:`NativeError` if it has not been built"""
-    global _stages6_lib
-    if _stages6_lib is None:
-        if not os.path.exists(STAGES6_LIB_PATH):
-            raise NativeError(
-                f"{STAGES6_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` or `make -C pydrobert-speech_amd/csrc` (there is no CPU fallback)"
-            )
-        try:  # (torch's HIP runtime first, as for lib())
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        loaded = ctypes.CDLL(STAGES6_LIB_PATH)
-        for name, (restype, argtypes) in STAGES6_SIGNATURES.items():
-            fn = getattr(loaded, name)  # AttributeError if the .so is stale
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _stages6_lib = loaded
-    return _stages6_lib
-
-
-def last_error() -> str:
-    return lib().pds_last_error().decode("utf-8", "replace")
-
-
-def check(rc: int, what: str) -> None:
-    if rc != PDS_OK:
-        msg = last_error()
-        if rc == -1:
-            raise ValueError(f"{what}: {msg}")
-        if rc == -3:
-            raise MemoryError(f"{what}: {msg}")
-        raise NativeError(f"{what}: {msg} (code {rc})")
-
-
-def check_stages(rc: int, what: str) -> None:
-    """:func:`check` for a call into the stages library, which keeps its own error string"""
-    if rc != PDS_OK:
-        msg = stages_lib().pds_stages_last_error().decode("utf-8", "replace")
-        if rc == -1:
-            raise ValueError(f"{what}: {msg}")
-        raise NativeError(f"{what}: {msg} (code {rc})")
-
-
-def check_stages2(rc: int, what: str) -> None:
-    """:func:`check` for a call into the second stages library, which keeps its own error string"""
-    if rc != PDS_OK:
-        msg = stages2_lib().pds_stages2_last_error().decode("utf-8", "replace")
-        if rc == -1:
-            raise ValueError(f"{what}: {msg}")
-        raise NativeError(f"{what}: {msg} (code {rc})")
-
-
-def check_stages3(rc: int, what: str) -> None:
-    """:func:`check` for a call into the third stages library, which keeps its own error string"""
-    if rc != PDS_OK:
-        msg = stages3_lib().pds_stages3_last_error().decode("utf-8", "replace")
-        if rc == -1:
-            raise ValueError(f"{what}: {msg}")
-        raise NativeError(f"{what}: {msg} (code {rc})")
-
-
-def check_stages4(rc: int, what: str) -> None:
-    """:func:`check` for a call into the fourth stages library, which keeps its own error string"""
-    if rc != PDS_OK:
-        msg = stages4_lib().pds_stages4_last_error().decode("utf-8", "replace")
-        if rc == -1:
-            raise ValueError(f"{what}: {msg}")
-        raise NativeError(f"{what}: {msg} (code {rc})")
-
-
-def check_stages5(rc: int, what: str) -> None:
-    """:func:`check` for a call into the fifth stages library, which keeps its own error string"""
-    if rc != PDS_OK:
-        msg = stages5_lib().pds_stages5_last_error().decode("utf-8", "replace")
-        if rc == -1:
-            raise ValueError(f"{what}: {msg}")
-        raise NativeError(f"{what}: {msg} (code {rc})")
-
-
-def check_stages6(rc: int, what: str) -> None:
-    """:func:`check` for a call into the sixth stages library, which keeps its own error string"""
-    if rc != PDS_OK:
-        msg = stages6_lib().pds_stages6_last_error().decode("utf-8", "replace")
-        if rc == -1:
-            raise ValueError(f"{what}: {msg}")
-        raise NativeError(f"{what}: {msg} (code {rc})")
+_CSRC = os.path.join(_HERE, "csrc")
+lib = Library("PDS_AMD_LIB", os.path.join(_CSRC, "libpds_amd.so"), SIGNATURES, "pds_last_error", {-3: MemoryError})
+# the first stages library is looked for in csrc/ wherever PDS_AMD_LIB points, the later ones beside the first library,
+# so that PDS_AMD_LIB moves them with it: an asymmetry that integrators rely on by now
+_BESIDE = os.path.dirname(lib.path)
+stages_lib = Library("PDS_AMD_STAGES_LIB", os.path.join(_CSRC, "libpds_amd_stages.so"), STAGES_SIGNATURES,
+                     "pds_stages_last_error")
+stages2_lib = Library("PDS_AMD_STAGES2_LIB", os.path.join(_BESIDE, "libpds_amd_stages2.so"), STAGES2_SIGNATURES,
+                      "pds_stages2_last_error")
+stages3_lib = Library("PDS_AMD_STAGES3_LIB", os.path.join(_BESIDE, "libpds_amd_stages3.so"), STAGES3_SIGNATURES,
+                      "pds_stages3_last_error")
+stages4_lib = Library("PDS_AMD_STAGES4_LIB", os.path.join(_BESIDE, "libpds_amd_stages4.so"), STAGES4_SIGNATURES,
+                      "pds_stages4_last_error")
+stages5_lib = Library("PDS_AMD_STAGES5_LIB", os.path.join(_BESIDE, "libpds_amd_stages5.so"), STAGES5_SIGNATURES,
+                      "pds_stages5_last_error")
+stages6_lib = Library("PDS_AMD_STAGES6_LIB", os.path.join(_BESIDE, "libpds_amd_stages6.so"), STAGES6_SIGNATURES,
+                      "pds_stages6_last_error")
+LIBRARIES = (lib, stages_lib, stages2_lib, stages3_lib, stages4_lib, stages5_lib, stages6_lib)
+(LIB_PATH, STAGES_LIB_PATH, STAGES2_LIB_PATH, STAGES3_LIB_PATH, STAGES4_LIB_PATH, STAGES5_LIB_PATH,
+ STAGES6_LIB_PATH) = (library.path for library in LIBRARIES)
+(check, check_stages, check_stages2, check_stages3, check_stages4, check_stages5,
+ check_stages6) = (library.check for library in LIBRARIES)
+last_error = lib.last_error
 
 
 def require_device():

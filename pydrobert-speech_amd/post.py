@@ -1776,7 +1776,7 @@ def _specaug_spans(nrows, limit=None):
     return spans
 
 
-class SpecAugment(PostProcessor):
+class SpecAugment(_pre._Seeded, PostProcessor):
     """SpecAugment (Park et al. 2019): a time warp, frequency masks and time masks over a feature matrix, for training
 
     `axis` of :func:`apply` is the *time* axis; the last remaining axis holds the columns.  The draws come from a
@@ -1845,6 +1845,7 @@ class SpecAugment(PostProcessor):
     """
 
     aliases = {"specaugment", "spec_augment", "specaug"}
+    _SEEDS_ERROR = "SpecAugment: one seed per utterance"
 
     def __init__(self, freq_masks: int = 2, freq_width: int = 10, time_masks: int = 2, time_width: int = 50,
                  time_ratio: float = 1.0, warp: int = 0, fill: Union[float, str] = 0.0, seed: Optional[int] = None):
@@ -1869,13 +1870,7 @@ class SpecAugment(PostProcessor):
         if seed is not None and (isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer))
                                  or int(seed) < 0):
             raise ValueError(f"SpecAugment: seed must be None or a non-negative integer, got {seed!r}")
-        self._given_seed = seed
-        self._seed = _pre._seed_state(seed)
-
-    @property
-    def seed(self) -> Optional[int]:
-        """the `seed` this object was built with"""
-        return self._given_seed
+        self._start_seed(seed)
 
     @property
     def plan_words(self) -> int:
@@ -1887,18 +1882,6 @@ class SpecAugment(PostProcessor):
         return (f"SpecAugment(freq_masks={self.freq_masks!r}, freq_width={self.freq_width!r}, "
                 f"time_masks={self.time_masks!r}, time_width={self.time_width!r}, time_ratio={self.time_ratio!r}, "
                 f"warp={self.warp!r}, fill={self.fill!r}, seed={self._given_seed!r})")
-
-    def _keys(self, B, seeds):
-        """one uint64 key per utterance: of `seeds` by ``Dither``'s rule, else the next B of the object's sequence"""
-        if seeds is None:
-            keys = np.empty(B, dtype=np.uint64)
-            for b in range(B):
-                self._seed = _pre._next_key(self._seed)
-                keys[b] = self._seed
-            return keys
-        if len(seeds) != B:
-            raise ValueError("SpecAugment: one seed per utterance")
-        return _pre.dither_keys(seeds)
 
     # ---- packed ragged batches ------------------------------------------------------
 

@@ -91,7 +91,76 @@ def dither_keys(seeds) -> np.ndarray:
     return np.fromiter((_next_key(_seed_state(int(s))) for s in seeds), dtype=np.uint64, count=len(seeds))
 
 
-class Dither(PreProcessor):
+class _Seeded:
+    """The seed of a stage that draws: `seed` as given, the state of the object's own sequence, and the one rule that
+    gives every utterance of a batch its key"""
+
+    _SEEDS_ERROR = "one seed per utterance"
+
+    def _start_seed(self, seed: Optional[int]) -> None:
+        self._given_seed = seed
+        self._seed = _seed_state(seed)
+
+    @property
+    def seed(self) -> Optional[int]:
+        """the `seed` this object was built with"""
+        return self._given_seed
+
+    def _keys(self, B: int, seeds) -> np.ndarray:
+        """uint64 per utterance: from `seeds` by :func:`dither_keys`, else the next `B` keys of the object's sequence"""
+        if seeds is None:
+            keys = np.empty(B, dtype=np.uint64)
+            for b in range(B):
+                self._seed = keys[b] = _next_key(self._seed)
+            return keys
+        if len(seeds) != B:
+            raise ValueError(self._SEEDS_ERROR)
+        return dither_keys(seeds)
+
+
+_U32 = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def _philox_draws(keys: np.ndarray, counter):
+    """x0..x3 of one Philox4x32-10 block on `counter` under every key of `keys` (uint64): four uint64 arrays of 32-bit
+    values (csrc/mix_rule.h: mix_draw, csrc/reverb_rule.h)"""
+    keys = np.asarray(keys, dtype=np.uint64)
+    k0, k1 = keys & _U32, keys >> _S32
+    c = [np.full(keys.shape, word, dtype=np.uint64) for word in counter]
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> _S32) ^ c[1] ^ k0, p1 & _U32, (p0 >> _S32) ^ c[3] ^ k1, p0 & _U32]
+        k0 = (k0 + np.uint64(0x9E3779B9)) & _U32
+        k1 = (k1 + np.uint64(0xBB67AE85)) & _U32
+    return c
+
+
+def _is_gpu_tensor(x) -> bool:
+    return bool(getattr(x, "is_cuda", False))
+
+
+def _check_packed(signal, offsets, lengths):
+    """What every packed waveform stage checks (Dither, AddNoise and Reverb): (offsets, lengths, B) on the host, or the
+    ``ValueError`` -- nothing here needs a device"""
+    import torch
+
+    if not _is_gpu_tensor(signal) or signal.dim() != 1:
+        raise ValueError("signal must be a 1-D GPU tensor")
+    if signal.dtype not in (torch.float32, torch.float64, torch.int16):
+        raise ValueError("signal must be float32, float64 or int16")
+    offs_h = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    lens_h = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    B = len(lens_h)
+    if len(offs_h) != B:
+        raise ValueError("one offset per length")
+    if B and (offs_h.min() < 0 or lens_h.min() < 0 or int((offs_h + lens_h).max()) > signal.numel()):
+        raise ValueError("the utterances lie outside signal")
+    return offs_h, lens_h, B
+
+
+class Dither(_Seeded, PreProcessor):
     """Add Gaussian noise of standard deviation `coeff` (aliases ``dither``, ``dithering``)
 
     `seed` makes the noise reproducible; each :func:`apply` advances it.  The noise of sample t of a signal depends on
@@ -104,13 +173,7 @@ class Dither(PreProcessor):
     def __init__(self, coeff: float = 1.0, seed: Optional[int] = None):
         super().__init__()
         self.coeff = coeff
-        self._given_seed = seed
-        self._seed = _seed_state(seed)
-
-    @property
-    def seed(self) -> Optional[int]:
-        """the `seed` this object was built with"""
-        return self._given_seed
+        self._start_seed(seed)
 
     def __repr__(self) -> str:
         # (what the object was built with and nothing of where it lies: a test id made of it is the same in every run)
@@ -158,25 +221,8 @@ class Dither(PreProcessor):
         """
         torch = _native.require_device()
         lib = _native.lib()
-        if not getattr(signal, "is_cuda", False) or signal.dim() != 1:
-            raise ValueError("signal must be a 1-D GPU tensor")
-        if signal.dtype not in (torch.float32, torch.float64, torch.int16):
-            raise ValueError("signal must be float32, float64 or int16")
-        offs_h = np.asarray(offsets, dtype=np.int64).reshape(-1)
-        lens_h = np.asarray(lengths, dtype=np.int64).reshape(-1)
-        B = len(lens_h)
-        if len(offs_h) != B:
-            raise ValueError("one offset per length")
-        if B and (offs_h.min() < 0 or lens_h.min() < 0 or int((offs_h + lens_h).max()) > signal.numel()):
-            raise ValueError("the utterances lie outside signal")
-        if seeds is None:
-            keys = np.empty(B, dtype=np.uint64)
-            for b in range(B):
-                self._seed = keys[b] = _next_key(self._seed)
-        else:
-            if len(seeds) != B:
-                raise ValueError("one seed per utterance")
-            keys = dither_keys(seeds)
+        offs_h, lens_h, B = _check_packed(signal, offsets, lengths)
+        keys = self._keys(B, seeds)
         signal = signal.contiguous()
         if signal.dtype == torch.int16:
             fn = lib.pds_dither_packed_i16_f32
@@ -491,27 +537,6 @@ _MIX_ENERGY_WAVES = 4  # chunks of a block of the energy kernel (MIX_ENERGY_WAVE
 _MIX_MAX_BLOCKS = (1 << 31) - 1  # blocks of one launch (MIX_MAX_BLOCKS)
 _MIX_MAX_UTTS = 65535  # utterances of one launch of the apply kernel (MIX_MAX_UTTS)
 _MIX_COUNTER = (0, 0, 0, 0x4D495831)  # the counter of the plan's Philox block (MIX_COUNTER_0 .. MIX_COUNTER_3)
-_U32 = np.uint64(0xFFFFFFFF)
-_S32 = np.uint64(32)
-
-
-def _is_gpu_tensor(x) -> bool:
-    return bool(getattr(x, "is_cuda", False))
-
-
-def _mix_draws(keys: np.ndarray):
-    """x0..x3 of the plan's Philox4x32-10 block under every key of `keys` (uint64): four uint64 arrays of 32-bit
-    values (csrc/mix_rule.h: mix_draw)"""
-    keys = np.asarray(keys, dtype=np.uint64)
-    k0, k1 = keys & _U32, keys >> _S32
-    c = [np.full(keys.shape, word, dtype=np.uint64) for word in _MIX_COUNTER]
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c[0]
-        p1 = np.uint64(0xCD9E8D57) * c[2]
-        c = [(p1 >> _S32) ^ c[1] ^ k0, p1 & _U32, (p0 >> _S32) ^ c[3] ^ k1, p0 & _U32]
-        k0 = (k0 + np.uint64(0x9E3779B9)) & _U32
-        k1 = (k1 + np.uint64(0xBB67AE85)) & _U32
-    return c
 
 
 def _mix_pick(x: np.ndarray, n: np.ndarray) -> np.ndarray:
@@ -524,26 +549,6 @@ def _mix_chunks(n):
     """chunks of segments of `n` samples (an integer or an array)"""
     n = np.asarray(n, dtype=np.int64)
     return np.where(n > 0, (n + (_MIX_CHUNK - 1)) // _MIX_CHUNK, 0)
-
-
-# what every packed waveform stage checks and counts (AddNoise and Reverb)
-
-def _check_packed(signal, offsets, lengths):
-    """(offsets, lengths, B) on the host, or the ``ValueError`` -- nothing here needs a device"""
-    import torch
-
-    if not _is_gpu_tensor(signal) or signal.dim() != 1:
-        raise ValueError("signal must be a 1-D GPU tensor")
-    if signal.dtype not in (torch.float32, torch.float64, torch.int16):
-        raise ValueError("signal must be float32, float64 or int16")
-    offs_h = np.asarray(offsets, dtype=np.int64).reshape(-1)
-    lens_h = np.asarray(lengths, dtype=np.int64).reshape(-1)
-    B = len(lens_h)
-    if len(offs_h) != B:
-        raise ValueError("one offset per length")
-    if B and (offs_h.min() < 0 or lens_h.min() < 0 or int((offs_h + lens_h).max()) > signal.numel()):
-        raise ValueError("the utterances lie outside signal")
-    return offs_h, lens_h, B
 
 
 def _chunk_bases(lens_h):
@@ -583,7 +588,7 @@ class NoisePlan(NamedTuple):
     applied: np.ndarray  #: bool, whether the utterance gets noise at all
 
 
-class AddNoise(PreProcessor):
+class AddNoise(_Seeded, PreProcessor):
     """Add a clip of a noise bank to every utterance at a signal-to-noise ratio drawn per utterance: the additive half
     of Kaldi's ``wav-reverberate --additive-signals --snrs`` (aliases ``add_noise``, ``additive_noise``, ``mix_noise``)
 
@@ -671,8 +676,7 @@ class AddNoise(PreProcessor):
         self._clip_offsets = (np.cumsum(lengths) - lengths).astype(np.int64)
         for table in (self._bank, self._clip_lengths, self._clip_offsets):
             table.flags.writeable = False
-        self._given_seed = seed
-        self._seed = _seed_state(seed)
+        self._start_seed(seed)
         self._on_device = {}  # device index -> [bank, its table (offsets, lengths, chunk bases), Pn or None]
 
     @staticmethod
@@ -707,11 +711,6 @@ class AddNoise(PreProcessor):
             raise ValueError(f"clip {k} is {clip.dtype}: a clip is float32, float64 or int16")
         return clip
 
-    @property
-    def seed(self) -> Optional[int]:
-        """the `seed` this object was built with"""
-        return self._given_seed
-
     num_clips = property(lambda self: len(self._clip_lengths), doc="K, the clips of the bank")
     clip_offsets = property(lambda self: self._clip_offsets, doc="int64 per clip: its first sample in the bank")
     clip_lengths = property(lambda self: self._clip_lengths, doc="int64 per clip: its samples")
@@ -723,16 +722,6 @@ class AddNoise(PreProcessor):
                 f"seed={self._given_seed!r})")
 
     # -- the plan ---------------------------------------------------------------------------------------------------
-
-    def _keys(self, B: int, seeds) -> np.ndarray:
-        if seeds is None:
-            keys = np.empty(B, dtype=np.uint64)
-            for b in range(B):
-                self._seed = keys[b] = _next_key(self._seed)
-            return keys
-        if len(seeds) != B:
-            raise ValueError("one seed per utterance")
-        return dither_keys(seeds)
 
     def plan(self, B: int, seeds=None, clips=None, snr_db=None) -> NoisePlan:
         """The plan of `B` utterances as numpy arrays: ``clip``, ``start``, ``snr_db``, ``ratio``, ``applied``
@@ -758,7 +747,7 @@ class AddNoise(PreProcessor):
             given_snr = np.asarray(snr_db, dtype=np.float64).reshape(-1)
             if len(given_snr) != B or not np.isfinite(given_snr).all():
                 raise ValueError("snr_db: one finite value per utterance")
-        x0, x1, x2, x3 = _mix_draws(self._keys(B, seeds))
+        x0, x1, x2, x3 = _philox_draws(self._keys(B, seeds), _MIX_COUNTER)
         clip = _mix_pick(x0, np.uint64(self.num_clips)) if given_clips is None else given_clips
         start = _mix_pick(x1, self._clip_lengths[clip].astype(np.uint64))
         lo, hi = self.snr_db
@@ -787,16 +776,12 @@ class AddNoise(PreProcessor):
 
     # -- the device side ----------------------------------------------------------------------------------------------
 
-    # (module-level helpers, shared with Reverb; kept reachable under their old names)
-    _check_packed = staticmethod(_check_packed)
-    _chunk_bases = staticmethod(_chunk_bases)
-    _apply_calls = staticmethod(_apply_calls)
-    _suffix = staticmethod(_suffix)
+    _chunk_bases = staticmethod(_chunk_bases)  # (a module-level helper; tools/mix_rate.py calls it on the object)
 
     def _chunk_sums(self, torch, lib, signal, table, B, total):
         """the chunk sums of the B segments of `signal` that rows 0..2 of `table` (offsets, lengths, chunk bases) name"""
         partials = torch.empty((total,), dtype=torch.float64, device=signal.device)
-        fn = getattr(lib, "pds_mix_chunk_energy_" + self._suffix(signal.dtype))
+        fn = getattr(lib, "pds_mix_chunk_energy_" + _suffix(signal.dtype))
         rc = fn(signal.data_ptr(), table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(), B, total,
                 partials.data_ptr(), torch.cuda.current_stream(signal.device).cuda_stream)
         _native.check_stages5(rc, "pds_mix_chunk_energy")
@@ -837,7 +822,7 @@ class AddNoise(PreProcessor):
     def energy_packed(self, signal, offsets, lengths):
         """float64 GPU tensor ``[B]``: the segment energy `E` of every utterance of a packed GPU buffer, as the
         definition sums it (utterance b is ``signal[offsets[b] : offsets[b] + lengths[b]]``)"""
-        offs_h, lens_h, B = self._check_packed(signal, offsets, lengths)
+        offs_h, lens_h, B = _check_packed(signal, offsets, lengths)
         bases, total = self._chunk_bases(lens_h)
         torch = _native.require_device()
         lib = _native.stages5_lib()
@@ -865,14 +850,14 @@ class AddNoise(PreProcessor):
         """
         import torch
 
-        offs_h, lens_h, B = self._check_packed(signal, offsets, lengths)
+        offs_h, lens_h, B = _check_packed(signal, offsets, lengths)
         if plan is None:
             if seeds is not None and len(seeds) != B:
                 raise ValueError("one seed per utterance")
         else:
             plan = self._check_plan(plan, B)
         bases, total = self._chunk_bases(lens_h)
-        calls = self._apply_calls(lens_h)
+        calls = _apply_calls(lens_h)
         if plan is None:
             plan = self.plan(B, seeds=seeds)
         torch = _native.require_device()
@@ -894,7 +879,7 @@ class AddNoise(PreProcessor):
             offs_h, lens_h, bases, self._clip_offsets[plan.clip], self._clip_lengths[plan.clip], plan.start,
             np.ascontiguousarray(plan.ratio).view(np.int64), plan.applied.astype(np.int64), plan.clip,
         ])).to(signal.device)
-        fn = getattr(lib, f"pds_mix_apply_{self._suffix(signal.dtype)}_{self._suffix(bank.dtype)}")
+        fn = getattr(lib, f"pds_mix_apply_{_suffix(signal.dtype)}_{_suffix(bank.dtype)}")
         with torch.cuda.device(signal.device):
             stream = torch.cuda.current_stream(signal.device).cuda_stream
             partials = self._chunk_sums(torch, lib, signal, table, B, total)
@@ -943,21 +928,6 @@ _REVERB_MAX_BLOCKS = (1 << 31) - 1  # blocks of one launch (REVERB_MAX_BLOCKS)
 _REVERB_COUNTER = (0, 0, 0, 0x52495231)  # the counter of the plan's Philox block (REVERB_COUNTER_0 .. REVERB_COUNTER_3)
 
 
-def _philox_draws(keys: np.ndarray, counter):
-    """x0..x3 of one Philox4x32-10 block on `counter` under every key of `keys` (uint64): four uint64 arrays of 32-bit
-    values"""
-    keys = np.asarray(keys, dtype=np.uint64)
-    k0, k1 = keys & _U32, keys >> _S32
-    c = [np.full(keys.shape, word, dtype=np.uint64) for word in counter]
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c[0]
-        p1 = np.uint64(0xCD9E8D57) * c[2]
-        c = [(p1 >> _S32) ^ c[1] ^ k0, p1 & _U32, (p0 >> _S32) ^ c[3] ^ k1, p0 & _U32]
-        k0 = (k0 + np.uint64(0x9E3779B9)) & _U32
-        k1 = (k1 + np.uint64(0xBB67AE85)) & _U32
-    return c
-
-
 def _reverb_even(units):
     return (units + 1) & ~np.int64(1)
 
@@ -969,7 +939,7 @@ class ReverbPlan(NamedTuple):
     applied: np.ndarray  #: bool, whether the utterance is reverberated at all
 
 
-class Reverb(PreProcessor):
+class Reverb(_Seeded, PreProcessor):
     """Convolve a room impulse response of a bank with every utterance: the reverberation half of Kaldi's
     ``wav-reverberate --impulse-response --shift-output --normalize-output`` (aliases ``reverb``, ``reverberate``,
     ``rir``)
@@ -1069,8 +1039,7 @@ class Reverb(PreProcessor):
                       self._rir_gains, *self._taps):
             table.flags.writeable = False
         self._spectra = None  # complex64 [sum of P_j, 1024], built at the first use
-        self._given_seed = seed
-        self._seed = _seed_state(seed)
+        self._start_seed(seed)
         self._on_device = {}  # device index -> (spectra, table (bases, partitions, peaks), twiddles)
 
     @staticmethod
@@ -1106,11 +1075,6 @@ class Reverb(PreProcessor):
         padded[: len(taps)] = taps
         return np.fft.fft(padded.reshape(parts, _REVERB_BLOCK), n=_REVERB_FFT, axis=1).astype(np.complex64)
 
-    @property
-    def seed(self) -> Optional[int]:
-        """the `seed` this object was built with"""
-        return self._given_seed
-
     num_rirs = property(lambda self: len(self._rir_lengths), doc="K, the room impulse responses of the bank")
     rir_lengths = property(lambda self: self._rir_lengths, doc="int64 per RIR: its taps")
     rir_peaks = property(lambda self: self._rir_peaks, doc="int64 per RIR: d, the shift of the output (0 without it)")
@@ -1122,16 +1086,6 @@ class Reverb(PreProcessor):
                 f"normalize_output={self.normalize_output!r}, seed={self._given_seed!r})")
 
     # -- the plan ---------------------------------------------------------------------------------------------------
-
-    def _keys(self, B: int, seeds) -> np.ndarray:
-        if seeds is None:
-            keys = np.empty(B, dtype=np.uint64)
-            for b in range(B):
-                self._seed = keys[b] = _next_key(self._seed)
-            return keys
-        if len(seeds) != B:
-            raise ValueError("one seed per utterance")
-        return dither_keys(seeds)
 
     def plan(self, B: int, seeds=None, rirs=None) -> ReverbPlan:
         """The plan of `B` utterances as numpy arrays: ``rir`` and ``applied``

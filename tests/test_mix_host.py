@@ -7,6 +7,7 @@ import ctypes
 import math
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -280,7 +281,7 @@ def many_keys():
 def test_draws_stay_in_range_over_ten_thousand_seeds(many_keys, K):
     lengths = [(1, 2, 16385)[k % 3] for k in range(K)]
     an = AddNoise([np.ones(n, np.float32) for n in lengths], snr_db=(-2.0, 31.0), prob=0.25)
-    x0, x1, x2, x3 = pre_module._mix_draws(many_keys)
+    x0, x1, x2, x3 = pre_module._philox_draws(many_keys, pre_module._MIX_COUNTER)
     clip = pre_module._mix_pick(x0, np.uint64(K))
     plan = an.plan(10000, seeds=range(10000))
     assert np.array_equal(plan.clip, clip)
@@ -397,9 +398,6 @@ def test_stages5_header_and_signature_table_name_the_same_set():
     applies = {f"pds_mix_apply_{x}_{z}" for x in ("f32", "f64", "i16") for z in ("f32", "f64", "i16")}
     assert {"pds_stages5_version", "pds_stages5_last_error", "pds_mix_gain", "pds_mix_chunk_energy_f32",
             "pds_mix_chunk_energy_f64", "pds_mix_chunk_energy_i16"} | applies <= set(declared)
-    others = (set(_native.SIGNATURES) | set(_native.STAGES_SIGNATURES) | set(_native.STAGES2_SIGNATURES)
-              | set(_native.STAGES3_SIGNATURES) | set(_native.STAGES4_SIGNATURES))
-    assert not set(declared) & others
     for name, args in declared.items():
         restype, argtypes = _native.STAGES5_SIGNATURES[name]
         count = 0 if args.strip() == "void" else len(args.split(","))
@@ -431,7 +429,8 @@ def test_mix_hip_includes_its_header_and_the_rule_and_nothing_else_of_the_projec
         make = fh.read()
     assert "STAGES5_LIB  = libpds_amd_stages5.so" in make and "STAGES5_OBJS = mix.o" in make
     assert re.search(r"^all:.*\$\(STAGES5_LIB\)", make, flags=re.M)
-    assert re.search(r"^mix\.o:.*\n\t.*-ffp-contract=off", make, flags=re.M)
+    command = subprocess.run(["make", "-n", "-B", "mix.o"], cwd=csrc, check=True, capture_output=True, text=True).stdout
+    assert "mix.hip" in command and "-ffp-contract=off" in command
     assert "STAGES4_OBJS = plp.o\n" in make  # the fifth library keeps the PLP kernels and no other
     with open(os.path.join(csrc, "pre.hip")) as fh:
         assert "mix" not in fh.read()  # nothing of it went into the first library
@@ -480,22 +479,6 @@ def test_stages5_library_exports_every_declared_symbol_and_reports_argument_erro
         _native.check_stages5(-1, "pds_mix_apply")
     with pytest.raises(_native.NativeError, match="code -2"):
         _native.check_stages5(-2, "pds_mix_apply")
-
-
-def test_the_library_is_found_beside_the_first_or_through_its_variable():
-    assert os.path.dirname(_native.STAGES5_LIB_PATH) == os.path.dirname(_native.LIB_PATH) or os.environ.get(
-        "PDS_AMD_STAGES5_LIB")
-    if not os.environ.get("PDS_AMD_STAGES5_LIB"):
-        assert os.path.basename(_native.STAGES5_LIB_PATH) == "libpds_amd_stages5.so"
-    src = open(_native.__file__).read()
-    assert 'os.environ.get("PDS_AMD_STAGES5_LIB")' in src
-
-
-def test_a_missing_library_is_an_error(monkeypatch, tmp_path):
-    monkeypatch.setattr(_native, "_stages5_lib", None)
-    monkeypatch.setattr(_native, "STAGES5_LIB_PATH", str(tmp_path / "libpds_amd_stages5.so"))
-    with pytest.raises(_native.NativeError, match="no CPU fallback"):
-        _native.stages5_lib()
 
 
 def test_no_cpu_path_without_a_device(monkeypatch):

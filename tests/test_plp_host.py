@@ -7,6 +7,7 @@ import ctypes
 import json
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -244,9 +245,6 @@ def test_stages4_header_and_signature_table_name_the_same_set():
     declared = dict(re.findall(r"\b(pds_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", code))
     assert set(declared) == set(_native.STAGES4_SIGNATURES), set(declared) ^ set(_native.STAGES4_SIGNATURES)
     assert {"pds_stages4_version", "pds_stages4_last_error", "pds_plp_rows_f32", "pds_plp_rows_f64"} <= set(declared)
-    others = (set(_native.SIGNATURES) | set(_native.STAGES_SIGNATURES) | set(_native.STAGES2_SIGNATURES)
-              | set(_native.STAGES3_SIGNATURES))
-    assert not set(declared) & others
     for name, args in declared.items():
         restype, argtypes = _native.STAGES4_SIGNATURES[name]
         count = 0 if args.strip() == "void" else len(args.split(","))
@@ -279,7 +277,8 @@ def test_plp_hip_includes_its_header_and_the_rule_and_nothing_else_of_the_projec
         make = fh.read()
     assert "STAGES4_LIB  = libpds_amd_stages4.so" in make and "STAGES4_OBJS = plp.o" in make
     assert re.search(r"^all:.*\$\(STAGES4_LIB\)", make, flags=re.M)
-    assert re.search(r"^plp\.o:.*\n\t.*-ffp-contract=off", make, flags=re.M)
+    command = subprocess.run(["make", "-n", "-B", "plp.o"], cwd=csrc, check=True, capture_output=True, text=True).stdout
+    assert "plp.hip" in command and "-ffp-contract=off" in command
     assert "STAGES3_OBJS = specaug.o\n" in make  # the third library keeps the SpecAugment kernels and no other
 
 
@@ -336,22 +335,6 @@ def test_stages4_library_exports_every_declared_symbol_and_reports_argument_erro
         _native.check_stages4(-1, "pds_plp_rows")
     with pytest.raises(_native.NativeError, match="code -2"):
         _native.check_stages4(-2, "pds_plp_rows")
-
-
-def test_the_library_is_found_beside_the_first_or_through_its_variable():
-    assert os.path.dirname(_native.STAGES4_LIB_PATH) == os.path.dirname(_native.LIB_PATH) or os.environ.get(
-        "PDS_AMD_STAGES4_LIB")
-    if not os.environ.get("PDS_AMD_STAGES4_LIB"):
-        assert os.path.basename(_native.STAGES4_LIB_PATH) == "libpds_amd_stages4.so"
-    src = open(_native.__file__).read()
-    assert 'os.environ.get("PDS_AMD_STAGES4_LIB")' in src
-
-
-def test_a_missing_library_is_an_error(monkeypatch, tmp_path):
-    monkeypatch.setattr(_native, "_stages4_lib", None)
-    monkeypatch.setattr(_native, "STAGES4_LIB_PATH", str(tmp_path / "libpds_amd_stages4.so"))
-    with pytest.raises(_native.NativeError, match="no CPU fallback"):
-        _native.stages4_lib()
 
 
 def test_no_cpu_path_without_a_device(monkeypatch):

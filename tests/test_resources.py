@@ -3,28 +3,9 @@
 A spilled kernel still computes the right values, so nothing else in the suite notices one; round 2 shipped float64
 -sample instantiations with up to 79 spilled registers.  The kernels the BASELINE.json workloads and the reference
 drivers' flows launch must have no scratch at all; the rest of the matrix is bounded."""
-import importlib.util
-import os
+from tests import resources
 
-import pytest
-
-from tests.conftest import ROOT
-
-LIB = os.path.join(ROOT, "pydrobert-speech_amd", "csrc", "libpds_amd.so")
-
-
-def _table():
-    spec = importlib.util.spec_from_file_location("resource_table", os.path.join(ROOT, "tools", "resource_table.py"))
-    rt = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(rt)
-    if not os.path.exists(LIB) or not os.path.exists(os.path.join(rt.LLVM, "llvm-readelf")):
-        pytest.skip("library or llvm-readelf not available")
-    rows, text = [], 0
-    for elf in rt.code_objects(LIB):
-        ks, t = rt.kernels_of(elf)
-        rows += ks
-        text += t
-    return {rt.short(n): k for n, k in rows}, text
+LIB = "libpds_amd.so"
 
 
 def _key(n1, n2, rows, maxw, minw, pre="F", seg=0, rsg="T", tin="f", tout="f", dlt=0, str_="F"):
@@ -63,7 +44,7 @@ DEFAULT_PATH = [
 
 
 def test_default_path_kernels_have_no_scratch():
-    table, _ = _table()
+    table, _ = resources.table(LIB)
     missing = [k for k in DEFAULT_PATH if k not in table]
     assert not missing, missing
     spilled = {k: table[k].get("private_segment_fixed_size", 0) for k in DEFAULT_PATH
@@ -75,7 +56,7 @@ def test_instantiation_matrix_stays_bounded():
     """ product build: fewer than 290 instantiations of the fused kernel (228 without the 58
     int16-sample ones that came after that item), device code below 4.3 MB (3.5 MB without them), and no kernel
     anywhere in the library with more than 40 spilled registers"""
-    table, text = _table()
+    table, text = resources.table(LIB)
     stft = [k for k in table if k.startswith("stft_wave<")]
     assert 0 < len(stft) < 290, len(stft)
     assert text < 4.3e6, text
@@ -88,7 +69,7 @@ def test_instantiation_matrix_stays_bounded():
 def test_short_integration_fft_kernels_fit_two_waves_per_simd_without_scratch():
     """csrc/si_fft.hip runs two waves per SIMD (256 registers each); its rework of round 3 started from instantiations
     that spilled 70-110 registers through hoisted per-row addresses -- none may come back"""
-    table, _ = _table()
+    table, _ = resources.table(LIB)
     si = {n: k for n, k in table.items() if "si_fft_kernel" in n}
     assert len(si) == 8, sorted(si)  # {1024-, 2048-point form} x {3, 5, 8, 16 window factors per lane and half}
     for name, k in si.items():

@@ -2,59 +2,29 @@
 CPU only): it holds the PCEN kernels and none named like a kernel of the other two libraries, none of them uses
 scratch or spills, and its device code is capped at 64 KiB like the first stages library's (DESIGN.md section 4.3:
 one capped library per 64 KiB of stage kernels)."""
-import importlib.util
-import os
+from tests import resources
+from tests.resources import TEXT_CAP
 
-import pytest
-
-from tests.conftest import ROOT
-
-CSRC = os.path.join(ROOT, "pydrobert-speech_amd", "csrc")
-LIB = os.path.join(CSRC, "libpds_amd_stages2.so")
-TEXT_CAP = 65536  # bytes of gfx950 .text: a cap, not a measurement
+LIB = "libpds_amd_stages2.so"
 KERNELS = ("pcen_smooth_rows_kernel", "pcen_compress_rows_kernel", "multistream_pcen_kernel")
 
 
-def _resource_table():
-    spec = importlib.util.spec_from_file_location("resource_table", os.path.join(ROOT, "tools", "resource_table.py"))
-    rt = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(rt)
-    return rt
-
-
-def _table(lib=LIB):
-    rt = _resource_table()
-    if not os.path.exists(lib) or not os.path.exists(os.path.join(rt.LLVM, "llvm-readelf")):
-        pytest.skip("library or llvm-readelf not available")
-    rows, text = [], 0
-    for elf in rt.code_objects(lib):
-        ks, t = rt.kernels_of(elf)
-        rows += ks
-        text += t
-    return {rt.short(n): k for n, k in rows}, text
-
-
 def test_the_library_holds_the_pcen_kernels_and_no_other():
-    table, _ = _table()
+    table, _ = resources.table(LIB)
     for kernel in KERNELS:
         names = sorted(n for n in table if kernel in n)
         assert len(names) == 2, (kernel, sorted(table))  # float32 and float64 of each
         # (mangled names: the template argument is `f` or `d`)
         assert any(kernel + "IfE" in n for n in names) and any(kernel + "IdE" in n for n in names), names
     assert all(any(kernel in n for kernel in KERNELS) for n in table), sorted(table)
-    # none named like a kernel of the other two libraries (their resource tests count kernels by these names)
-    for other in ("libpds_amd.so", "libpds_amd_stages.so"):
-        path = os.path.join(CSRC, other)
-        if not os.path.exists(path):
-            continue
-        theirs, _ = _table(path)
-        assert theirs and not set(theirs) & set(table)
+    # none named like a kernel of the other libraries (their resource tests count kernels by these names; that no
+    # other library holds a kernel of this one's names is tests/test_native_libraries.py's)
     for word in ("sliding", "vad_energy", "select_rows", "resample", "stft_wave", "multistream_cmvn"):
         assert not any(word in n for n in table), word
 
 
 def test_no_kernel_has_scratch_or_spills():
-    table, _ = _table()
+    table, _ = resources.table(LIB)
     assert len(table) == 6
     for name, k in table.items():
         assert k.get("private_segment_fixed_size", 0) == 0, (name, k)
@@ -62,6 +32,6 @@ def test_no_kernel_has_scratch_or_spills():
 
 
 def test_device_code_stays_under_its_cap():
-    _, text = _table()
+    _, text = resources.table(LIB)
     print("device code of the second stages library:", text, "bytes")
     assert 0 < text <= TEXT_CAP, text

@@ -2,40 +2,15 @@
 CPU only): it holds the PLP kernels and none named like a kernel of the other four libraries, float32 and float64 of
 each, none of them uses scratch or spills, and its device code is capped at 64 KiB like the other stages libraries'
 (one capped library per family of stage kernels)."""
-import importlib.util
-import os
+from tests import resources
+from tests.resources import TEXT_CAP
 
-import pytest
-
-from tests.conftest import ROOT
-
-CSRC = os.path.join(ROOT, "pydrobert-speech_amd", "csrc")
-LIB = os.path.join(CSRC, "libpds_amd_stages4.so")
-TEXT_CAP = 65536  # bytes of gfx950 .text: a cap, not a measurement
+LIB = "libpds_amd_stages4.so"
 TYPED_KERNELS = ("plp_rows_kernel",)
 
 
-def _resource_table():
-    spec = importlib.util.spec_from_file_location("resource_table", os.path.join(ROOT, "tools", "resource_table.py"))
-    rt = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(rt)
-    return rt
-
-
-def _table(lib=LIB):
-    rt = _resource_table()
-    if not os.path.exists(lib) or not os.path.exists(os.path.join(rt.LLVM, "llvm-readelf")):
-        pytest.skip("library or llvm-readelf not available")
-    rows, text = [], 0
-    for elf in rt.code_objects(lib):
-        ks, t = rt.kernels_of(elf)
-        rows += ks
-        text += t
-    return {rt.short(n): k for n, k in rows}, text
-
-
 def test_the_library_holds_the_plp_kernels_and_no_other():
-    table, _ = _table()
+    table, _ = resources.table(LIB)
     for kernel in TYPED_KERNELS:
         names = sorted(n for n in table if kernel in n)
         assert len(names) == 2, (kernel, sorted(table))  # float32 and float64 of each
@@ -44,21 +19,15 @@ def test_the_library_holds_the_plp_kernels_and_no_other():
         assert any(kernel + "IdE" in n or kernel + "<double>" in n for n in names), names
     assert all("plp_" in n for n in table), sorted(table)
     assert all(any(kernel in n for kernel in TYPED_KERNELS) for n in table), sorted(table)
-    # none named like a kernel of the other four libraries (their resource tests count kernels by these names)
-    for other in ("libpds_amd.so", "libpds_amd_stages.so", "libpds_amd_stages2.so", "libpds_amd_stages3.so"):
-        path = os.path.join(CSRC, other)
-        if not os.path.exists(path):
-            continue
-        theirs, _ = _table(path)
-        assert theirs and not set(theirs) & set(table)
-        assert not any("plp_" in n for n in theirs), other
+    # none named like a kernel of the other libraries (their resource tests count kernels by these names; that no
+    # other library holds a kernel of this one's names, or one with "plp_" in it, is tests/test_native_libraries.py's)
     for word in ("sliding", "vad_energy", "select_rows", "resample", "stft_wave", "multistream", "pcen", "specaug",
                  "cepstra"):
         assert not any(word in n for n in table), word
 
 
 def test_no_kernel_has_scratch_or_spills():
-    table, _ = _table()
+    table, _ = resources.table(LIB)
     assert len(table) == 2
     for name, k in table.items():
         print(name, "vgpr", k.get("vgpr_count"), "sgpr", k.get("sgpr_count"), "static lds",
@@ -69,6 +38,6 @@ def test_no_kernel_has_scratch_or_spills():
 
 
 def test_device_code_stays_under_its_cap():
-    _, text = _table()
+    _, text = resources.table(LIB)
     print("device code of the fourth stages library:", text, "bytes")
     assert 0 < text <= TEXT_CAP, text

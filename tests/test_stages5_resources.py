@@ -3,41 +3,16 @@ CPU only): it holds the three families of noise-mixing kernels with the expected
 named like a kernel of the other five libraries, none of them uses scratch, spills or static LDS, and its device code
 is capped at 64 KiB like the other stages libraries' (one capped library per family of stage
 kernels)."""
-import importlib.util
-import os
+from tests import resources
+from tests.resources import TEXT_CAP
 
-import pytest
-
-from tests.conftest import ROOT
-
-CSRC = os.path.join(ROOT, "pydrobert-speech_amd", "csrc")
-LIB = os.path.join(CSRC, "libpds_amd_stages5.so")
-TEXT_CAP = 65536  # bytes of gfx950 .text: a cap, not a measurement
+LIB = "libpds_amd_stages5.so"
 # (mangled names have the template arguments as `f`, `d` and `s`, demangled ones spell them out)
 TYPES = (("f", "float"), ("d", "double"), ("s", "short"))
 
 
-def _resource_table():
-    spec = importlib.util.spec_from_file_location("resource_table", os.path.join(ROOT, "tools", "resource_table.py"))
-    rt = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(rt)
-    return rt
-
-
-def _table(lib=LIB):
-    rt = _resource_table()
-    if not os.path.exists(lib) or not os.path.exists(os.path.join(rt.LLVM, "llvm-readelf")):
-        pytest.skip("library or llvm-readelf not available")
-    rows, text = [], 0
-    for elf in rt.code_objects(lib):
-        ks, t = rt.kernels_of(elf)
-        rows += ks
-        text += t
-    return {rt.short(n): k for n, k in rows}, text
-
-
 def test_the_library_holds_the_three_kernel_families_and_no_other():
-    table, _ = _table()
+    table, _ = resources.table(LIB)
     energy = sorted(n for n in table if "mix_chunk_energy_kernel" in n)
     assert len(energy) == 3, sorted(table)  # float, double and int16_t segments
     for short, long in TYPES:
@@ -52,22 +27,15 @@ def test_the_library_holds_the_three_kernel_families_and_no_other():
             assert any(f"mix_apply_kernelI{xs}{zs}E" in n or f"mix_apply_kernel<{xl}, {zl}>" in n for n in apply), (
                 xl, zl, apply)
     assert len(table) == 13 and all("mix_" in n for n in table), sorted(table)
-    # none named like a kernel of the other five libraries (their resource tests count kernels by these names)
-    for other in ("libpds_amd.so", "libpds_amd_stages.so", "libpds_amd_stages2.so", "libpds_amd_stages3.so",
-                  "libpds_amd_stages4.so"):
-        path = os.path.join(CSRC, other)
-        if not os.path.exists(path):
-            continue
-        theirs, _ = _table(path)
-        assert theirs and not set(theirs) & set(table)
-        assert not any("mix_" in n for n in theirs), other
+    # none named like a kernel of the other libraries (their resource tests count kernels by these names; that no
+    # other library holds a kernel of this one's names, or one with "mix_" in it, is tests/test_native_libraries.py's)
     for word in ("sliding", "vad_energy", "select_rows", "resample", "stft_wave", "multistream", "pcen", "specaug",
                  "cepstra", "plp_", "dither"):
         assert not any(word in n for n in table), word
 
 
 def test_no_kernel_has_scratch_spills_or_static_lds():
-    table, _ = _table()
+    table, _ = resources.table(LIB)
     assert len(table) == 13
     for name, k in table.items():
         print(name, "vgpr", k.get("vgpr_count"), "sgpr", k.get("sgpr_count"), "static lds",
@@ -79,6 +47,6 @@ def test_no_kernel_has_scratch_spills_or_static_lds():
 
 
 def test_device_code_stays_under_its_cap():
-    _, text = _table()
+    _, text = resources.table(LIB)
     print("device code of the fifth stages library:", text, "bytes")
     assert 0 < text <= TEXT_CAP, text

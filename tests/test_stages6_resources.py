@@ -4,43 +4,17 @@ named like a kernel of the other six libraries, none of them uses scratch or spi
 kernels (eight transposition areas and the twiddle table) leaves room for two blocks per CU in 160 KB, and its device
 code is capped at 64 KiB like the other stages libraries' (one capped library per family of stage
 kernels)."""
-import importlib.util
-import os
+from tests import resources
+from tests.resources import LDS_PER_CU, TEXT_CAP
 
-import pytest
-
-from tests.conftest import ROOT
-
-CSRC = os.path.join(ROOT, "pydrobert-speech_amd", "csrc")
-LIB = os.path.join(CSRC, "libpds_amd_stages6.so")
-TEXT_CAP = 65536  # bytes of gfx950 .text: a cap, not a measurement
-LDS_PER_CU = 160 * 1024
+LIB = "libpds_amd_stages6.so"
 TRANSFORM_LDS = 8 * 32 * 33 * 8 + 32 * 32 * 8  # eight half waves' transposition areas and the twiddle table
 # (mangled names have the template arguments as `f`, `d` and `s`, demangled ones spell them out)
 TYPES = (("f", "float"), ("d", "double"), ("s", "short"))
 
 
-def _resource_table():
-    spec = importlib.util.spec_from_file_location("resource_table", os.path.join(ROOT, "tools", "resource_table.py"))
-    rt = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(rt)
-    return rt
-
-
-def _table(lib=LIB):
-    rt = _resource_table()
-    if not os.path.exists(lib) or not os.path.exists(os.path.join(rt.LLVM, "llvm-readelf")):
-        pytest.skip("library or llvm-readelf not available")
-    rows, text = [], 0
-    for elf in rt.code_objects(lib):
-        ks, t = rt.kernels_of(elf)
-        rows += ks
-        text += t
-    return {rt.short(n): k for n, k in rows}, text
-
-
 def test_the_library_holds_the_three_kernel_families_and_no_other():
-    table, _ = _table()
+    table, _ = resources.table(LIB)
     spectra = sorted(n for n in table if "reverb_spectra_kernel" in n)
     assert len(spectra) == 3, sorted(table)  # float, double and int16_t samples
     for short, long in TYPES:
@@ -49,22 +23,15 @@ def test_the_library_holds_the_three_kernel_families_and_no_other():
     assert len([n for n in table if "reverb_convolve_kernel" in n]) == 1, sorted(table)  # the copy's dtype an argument
     assert len([n for n in table if "reverb_scale_kernel" in n]) == 1, sorted(table)
     assert len(table) == 5 and all("reverb_" in n for n in table), sorted(table)
-    # none named like a kernel of the other six libraries (their resource tests count kernels by these names)
-    for other in ("libpds_amd.so", "libpds_amd_stages.so", "libpds_amd_stages2.so", "libpds_amd_stages3.so",
-                  "libpds_amd_stages4.so", "libpds_amd_stages5.so"):
-        path = os.path.join(CSRC, other)
-        if not os.path.exists(path):
-            continue
-        theirs, _ = _table(path)
-        assert theirs and not set(theirs) & set(table)
-        assert not any("reverb_" in n for n in theirs), other
+    # none named like a kernel of the other libraries (their resource tests count kernels by these names; that no
+    # other library holds a kernel of this one's names, or one with "reverb_" in it, is tests/test_native_libraries.py's)
     for word in ("mix_", "sliding", "resample", "pcen", "specaug", "plp_", "dither", "cepstra", "multistream",
                  "stft_wave", "vad_energy", "select_rows"):
         assert not any(word in n for n in table), word
 
 
 def test_no_kernel_has_scratch_or_spills_and_lds_is_the_transform_areas():
-    table, _ = _table()
+    table, _ = resources.table(LIB)
     assert len(table) == 5
     for name, k in table.items():
         print(name, "vgpr", k.get("vgpr_count"), "agpr", k.get("agpr_count"), "sgpr", k.get("sgpr_count"), "static lds",
@@ -85,6 +52,6 @@ def test_no_kernel_has_scratch_or_spills_and_lds_is_the_transform_areas():
 
 
 def test_device_code_stays_under_its_cap():
-    _, text = _table()
+    _, text = resources.table(LIB)
     print("device code of the sixth stages library:", text, "bytes")
     assert 0 < text <= TEXT_CAP, text

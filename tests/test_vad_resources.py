@@ -1,32 +1,13 @@
 """The energy VAD's kernels in the stages library, read from its gfx950 code objects (tools/resource_table.py; CPU
 only): the decision kernel in float32 and float64 and ONE selection kernel (rows are copied as 32-bit words whatever
 their type), none with scratch or spills.  The library's size cap is tests/test_sliding_resources.py's."""
-import importlib.util
-import os
+from tests import resources
 
-import pytest
-
-from tests.conftest import ROOT
-
-LIB = os.path.join(ROOT, "pydrobert-speech_amd", "csrc", "libpds_amd_stages.so")
-
-
-def _table():
-    spec = importlib.util.spec_from_file_location("resource_table", os.path.join(ROOT, "tools", "resource_table.py"))
-    rt = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(rt)
-    if not os.path.exists(LIB) or not os.path.exists(os.path.join(rt.LLVM, "llvm-readelf")):
-        pytest.skip("library or llvm-readelf not available")
-    rows, text = [], 0
-    for elf in rt.code_objects(LIB):
-        ks, t = rt.kernels_of(elf)
-        rows += ks
-        text += t
-    return {rt.short(n): k for n, k in rows}, text
+LIB = "libpds_amd_stages.so"
 
 
 def test_the_library_holds_two_decision_kernels_and_one_selection_kernel():
-    table, text = _table()
+    table, text = resources.table(LIB)
     decide = sorted(n for n in table if "vad_energy_kernel" in n)
     select = sorted(n for n in table if "select_rows_kernel" in n)
     assert len(decide) == 2 and len(select) == 1, sorted(table)
